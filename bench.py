@@ -34,6 +34,11 @@ fused SDF query on the matrix pipe; HIP events on its launch stream inside the t
 oracle tick of configs[1] on the host cores + the parity of that very run as scalars).  The FULL record -- `rooflines` of the other
 heavy kernels, `predicted_scaling`, the whole parity report, per-stage CPU seconds -- is written to bench_detail.json beside this script
 ($D3H_BENCH_DETAIL overrides; emit()), never to stdout: the round-4 line had grown to 23 KB and the driver could not parse it.
+
+--dump-outputs DIR: after the timed steps, the losses of the last one, the parameters after it and their gradients as DIR/<name>.npy
+(step_outputs(), dump_outputs()).  The steps of the headline scene run at learning rate zero (every kernel of the step still runs, Adam
+included), and the start-up is deterministic: with the same arguments every timed step gets the same inputs in every run, and runs differ
+only by the summation order of the float atomics inside one step.
 """
 import argparse
 import ctypes
@@ -359,6 +364,46 @@ def cpu_baseline_config2(sc2):
             'parity_summary': parity_summary(rep)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs writes at most this much; larger arrays keep a fixed, seeded sample of their elements
+
+
+def step_outputs(sc):
+    """{name: float array} of what a caller of the timed step holds after its last call: the loss values it returned (`loss.*`), the
+    parameters its optimiser step holds (`param.*`) and the gradients it computed for them (`grad.*`)."""
+    import numpy as np
+    import torch
+    names = {}
+    for prefix, mod in (('geometry', sc.geometry), ('material', sc.material['kd_ks'])):
+        for n, p in mod.named_parameters():
+            names.setdefault(id(p), f'{prefix}.{n}')
+    for n, v in vars(sc.FLAGS).items():
+        if torch.is_tensor(v):
+            names.setdefault(id(v), f'flags.{n}')
+    groups = sc.opt_geo.param_groups + (sc.opt_mat.param_groups if sc.opt_mat is not None else [])
+    host = lambda t: t.detach().cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    out = {f'loss.{k}': host(v) for k, v in sc.last.items() if torch.is_tensor(v)}
+    for g in groups:
+        for p in g['params']:
+            n = names[id(p)]
+            out[f'param.{n}'] = host(p)
+            if p.grad is not None:
+                out[f'grad.{n}'] = host(p.grad)
+    return out
+
+
+def dump_outputs(arrays, path):
+    """`arrays` -> path/<name>.npy, DUMP_LIMIT_BYTES in all: when the whole set is larger, every array above an equal share of the limit
+    keeps that share of its elements (flattened), at indices drawn from a fixed seed"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    big = sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES
+    for name, a in sorted(arrays.items()):
+        if big and a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def timed_steps(step, k, warm=3):
     """ms per step of `step()` over k steps after `warm` untimed ones (one process, stream-synchronised on both sides)"""
     import gc
@@ -488,11 +533,15 @@ def main():
     ap.add_argument('--no-extras', action='store_true', help='skip the 12-buffer rate')
     ap.add_argument('--all-buffers', action='store_true', help='time the step with all 12 reference buffers composited + antialiased (render.py:430-449) instead of the loss-consumed three')
     ap.add_argument('--prefit', type=int, default=300)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed (losses, updated parameters, their gradients) as DIR/<name>.npy')
     args = ap.parse_args()
     args.config = int(args.config) if str(args.config).isdigit() else str(args.config)
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))       # parent: no GPU call before or after
     claim_stdout()                     # (before any library that may print to stdout is loaded)
@@ -576,15 +625,23 @@ def main():
             g = np.load(gpath)
             lp.load_state_dict({f'lin{k}.model.1.weight': torch.from_numpy(g[f'alex.lin{k}']) for k in range(5)}, strict=False)
         name += '; + LPIPS (alex trunk, random init; vendored linear layers)'
+    # the SDF pre-fit of the start-up runs on the library GEMMs: the fused backward sums its weight gradients with float atomics, and 300 Adam
+    # steps turn that into a different starting state (and targets) in every run; this way the timed steps get the same inputs every time
     sc = scene.Scene(device=dev, prefit_steps=args.prefit, visualize_watertight=True, dist_world=world, dist_rank=rank, lpips=lp,
                      frame_seed=1234 + rank * cfg['n_frames'],
-                     flags_hook=lambda F: (setattr(F, 'eikonal_samples', EIK_TOTAL), setattr(F, 'use_perceptual_normal_loss', args.config == 'f3c')), **cfg)
+                     flags_hook=lambda F: (setattr(F, 'eikonal_samples', EIK_TOTAL), setattr(F, 'use_perceptual_normal_loss', args.config == 'f3c'),
+                                           setattr(F, 'prefit_with_library_path', True)), **cfg)
     if world > 1:      # identical shared parameters on every rank
         for p in sc.shared_params:
             dist.broadcast(p.data, src=0)
         if shard:
             # each rank sweeps 1/N of the tet grid (sdf all-gathered, d(sdf) reduce-scattered) and draws 50 000 / N eikonal samples
             sc.enable_work_sharding(EIK_TOTAL)
+    # Every warm-up and timed step runs the whole training step -- forward, backward, gradient all-reduce, the fused Adam launch -- at learning
+    # rate zero, so each one starts from the same parameters.  Training on would make the last step's inputs depend on every earlier step's
+    # float-atomic summation order (Adam turns those last-bit differences into different parameters within a few steps): the same arguments
+    # would not give the same inputs, and two builds could not be compared output for output (--dump-outputs).
+    sc.freeze_learning()
 
     def sync():
         if world > 1:
@@ -599,6 +656,8 @@ def main():
         for _ in range(args.warmup):
             {'split': sc.step_split, 'seq': sc.step_seq}.get(cfg['loss_set'], sc.step)()
         ms = virtual_rank_ms(sc, W, r, mode, args.steps)
+        if args.dump_outputs:
+            dump_outputs(step_outputs(sc), args.dump_outputs)
         from d3h import dist_ops as D
         nb = 4 * sum(p.numel() for p in sc._bucket_members())
         n_grid = sc.geometry.verts.shape[0]
@@ -651,6 +710,8 @@ def main():
     dt = time.time() - t0
     marks.append(time.perf_counter())
     lib.d3h_timing_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(sc), args.dump_outputs)         # before anything below steps the scene again
     recs = collect_kernel_timing(lib) if rank == 0 else []
     coll = sc.coll_timing
     sc.coll_timing = None
@@ -927,7 +988,7 @@ def main():
                       'buffers': "what tick_init reads (shaded, geometric_normal, msdf_image): the default of tick_* through the unmodified train.py; FLAGS.render_buffers = 'all' gives all_12_buffers_iters_per_s",
                       'parallelism': f'frame-parallel dp{world}' + (' + SDF sweep and eikonal samples sharded over the ranks' if shard else
                                                                      (' (frame-independent work replicated on every rank)' if world > 1 else '')),
-                      'optimizer': 'one-launch fused Adam (d3h.optim.FusedAdam)' if sc.opt is not None else 'torch.optim.Adam(fused=True) x2',
+                      'optimizer': ('one-launch fused Adam (d3h.optim.FusedAdam)' if sc.opt is not None else 'torch.optim.Adam(fused=True) x2') + ' at learning rate 0',
                       'covered_pixels_last_render': cov_px, 'loss': last_loss,
                       'step_entry_intervals_ms': (lambda d: {'p50': d[len(d) // 2], 'p99': d[min(len(d) - 1, int(len(d) * 0.99))], 'max': d[-1],
                                                              'note': 'host clock between consecutive step entries inside the timed region (the host '
