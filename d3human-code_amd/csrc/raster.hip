@@ -352,9 +352,13 @@ __global__ __launch_bounds__(256) void raster_tile_kernel(const float* __restric
 }
 
 // rasterize backward, per pixel: d(u, v) at pixel (px, py) of triangle f -> the nine d(x), d(y), d(w) of its three clip positions (out) and the
-// three vertex ids (vi)
-__device__ __forceinline__ void raster_bwd_pixel(const float* __restrict__ posb, const int* __restrict__ tri, int f, int px, int py, int H, int W,
-                                                 float gu, float gv, float (&out)[9], int (&vi)[3]) {
+// three vertex ids (vi).  DB: also the adjoint of the pixel derivatives db = (du/dX, du/dY, dv/dX, dv/dY) of resolve_pixel (gdb).  They are
+// (dn{x,y}_0 - u dS{x,y}) / S and (dn{x,y}_1 - v dS{x,y}) / S in pixel units, with dnx_k = (Y_{k+1} - Y_{k+2}) q_k, dny_k = (X_{k+2} - X_{k+1}) q_k
+// and dS{x,y} = sum_k dn{x,y}_k: gdb adds into gu / gv (the existing path), gives S a direct adjoint (gS), and lands on X, Y, q through
+// dnx / dny directly.
+template <bool DB>
+__device__ __forceinline__ void raster_bwd_pixel_t(const float* __restrict__ posb, const int* __restrict__ tri, int f, int px, int py, int H, int W,
+                                                   float gu, float gv, float4 gdb, float (&out)[9], int (&vi)[3]) {
     TriSetup t = load_tri(posb, tri, f);
     float fx = (px + 0.5f) * (2.0f / W) - 1.0f, fy = (py + 0.5f) * (2.0f / H) - 1.0f;
     float a[3];
@@ -362,11 +366,40 @@ __device__ __forceinline__ void raster_bwd_pixel(const float* __restrict__ posb,
     float n0 = a[0] * t.q[0], n1 = a[1] * t.q[1], n2 = a[2] * t.q[2];
     float S = n0 + n1 + n2, iS = 1.0f / S;
     float u = n0 * iS, v = n1 * iS;
+    float ga[3], gq[3], gX[3] = {0.f, 0.f, 0.f}, gY[3] = {0.f, 0.f, 0.f};
+    float gS = 0.f, gqd[3] = {0.f, 0.f, 0.f};
+    if constexpr (DB) {
+        const float dax[3] = {t.Y[1] - t.Y[2], t.Y[2] - t.Y[0], t.Y[0] - t.Y[1]};
+        const float day[3] = {t.X[2] - t.X[1], t.X[0] - t.X[2], t.X[1] - t.X[0]};
+        const float dSx = dax[0] * t.q[0] + dax[1] * t.q[1] + dax[2] * t.q[2], dSy = day[0] * t.q[0] + day[1] * t.q[1] + day[2] * t.q[2];
+        const float h0 = gdb.x * (2.0f / W) * iS, h1 = gdb.y * (2.0f / H) * iS, h2 = gdb.z * (2.0f / W) * iS, h3 = gdb.w * (2.0f / H) * iS;
+        gS = -(h0 * (dax[0] * t.q[0] - u * dSx) + h1 * (day[0] * t.q[0] - u * dSy) + h2 * (dax[1] * t.q[1] - v * dSx) +
+               h3 * (day[1] * t.q[1] - v * dSy)) * iS;
+        gu -= h0 * dSx + h1 * dSy;
+        gv -= h2 * dSx + h3 * dSy;
+        const float gSx = -(u * h0 + v * h2), gSy = -(u * h1 + v * h3);
+        const float gdnx[3] = {h0 + gSx, h2 + gSx, gSx}, gdny[3] = {h1 + gSy, h3 + gSy, gSy};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            int j = (k + 1) % 3, l = (k + 2) % 3;
+            gqd[k] = gdnx[k] * dax[k] + gdny[k] * day[k];
+            const float gx = gdnx[k] * t.q[k], gy = gdny[k] * t.q[k];
+            gY[j] += gx; gY[l] -= gx;               // dax_k = Y_j - Y_l
+            gX[l] += gy; gX[j] -= gy;               // day_k = X_l - X_j
+        }
+    }
     float dotg = gu * u + gv * v;
     float gn[3] = {(gu - dotg) * iS, (gv - dotg) * iS, -dotg * iS};
-    float ga[3], gq[3], gX[3] = {0.f, 0.f, 0.f}, gY[3] = {0.f, 0.f, 0.f};
+    if constexpr (DB) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gn[k] += gS;
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) { ga[k] = gn[k] * t.q[k]; gq[k] = gn[k] * a[k]; }
+    if constexpr (DB) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gq[k] += gqd[k];
+    }
     // a_i = (X_j - fx)(Y_k - fy) - (Y_j - fy)(X_k - fx), (j, k) = (i+1, i+2)
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -386,6 +419,10 @@ __device__ __forceinline__ void raster_bwd_pixel(const float* __restrict__ posb,
         out[3 * k + 1] = gY[k] * q;
         out[3 * k + 2] = -gqk * q * q;
     }
+}
+__device__ __forceinline__ void raster_bwd_pixel(const float* __restrict__ posb, const int* __restrict__ tri, int f, int px, int py, int H, int W,
+                                                 float gu, float gv, float (&out)[9], int (&vi)[3]) {
+    raster_bwd_pixel_t<false>(posb, tri, f, px, py, H, W, gu, gv, make_float4(0.f, 0.f, 0.f, 0.f), out, vi);
 }
 
 // rasterize backward: d(u, v) -> d(clip positions)
@@ -409,6 +446,44 @@ __global__ __launch_bounds__(256) void raster_bwd_kernel(const float* __restrict
     if (live) {
         int rem = (int)(i % ((size_t)H * W));
         raster_bwd_pixel(pos + (size_t)b * pos_bstride, tri, id - 1, rem % W, rem / W, H, W, gu, gv, out, vi);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float sx = d3h_seg_sum(out[3 * k + 0], lane, sg.start);
+        float sy = d3h_seg_sum(out[3 * k + 1], lane, sg.start);
+        float sw = d3h_seg_sum(out[3 * k + 2], lane, sg.start);
+        if (sg.tail && live) {
+            float* dp = d_pos + (size_t)b * pos_bstride + 4 * (size_t)vi[k];
+            atomicAdd(dp + 0, sx);
+            atomicAdd(dp + 1, sy);
+            atomicAdd(dp + 3, sw);
+        }
+    }
+}
+
+// rasterize backward with the pixel derivatives: d(u, v) (g_rast, may be NULL) and d(du/dX, du/dY, dv/dX, dv/dY) (g_db, may be NULL) ->
+// d(clip positions).  A pixel is live when either gradient is non-zero; the run reduction is raster_bwd_kernel's.
+__global__ __launch_bounds__(256) void raster_bwd_db_kernel(const float* __restrict__ pos, int pos_bstride, const int* __restrict__ tri, int H, int W,
+                                                            int nb, const float* __restrict__ rast, const float* __restrict__ g_rast,
+                                                            const float* __restrict__ g_db, float* __restrict__ d_pos) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    size_t n = (size_t)nb * H * W;
+    const int lane = threadIdx.x & 63;
+    const bool inb = i < n;
+    float4 r = inb ? *(const float4*)(rast + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int id = (int)r.w;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 g = (inb && id > 0 && g_rast) ? *(const float4*)(g_rast + 4 * i) : z4;
+    const float4 gd = (inb && id > 0 && g_db) ? *(const float4*)(g_db + 4 * i) : z4;
+    const bool live = id > 0 && !(g.x == 0.f && g.y == 0.f && gd.x == 0.f && gd.y == 0.f && gd.z == 0.f && gd.w == 0.f);
+    if (__ballot(live) == 0ull) return;                 // wave-uniform
+    const int b = inb ? (int)(i / ((size_t)H * W)) : 0;
+    const D3hSeg sg = d3h_seg_runs(live ? id + (b << 24) : -1, lane);
+    float out[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int vi[3] = {0, 0, 0};
+    if (live) {
+        int rem = (int)(i % ((size_t)H * W));
+        raster_bwd_pixel_t<true>(pos + (size_t)b * pos_bstride, tri, id - 1, rem % W, rem / W, H, W, g.x, g.y, gd, out, vi);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -507,6 +582,121 @@ __global__ __launch_bounds__(256) void interp_bwd_kernel(const float* __restrict
         }
     }
     if (d_rast && inb) *(float4*)(d_rast + 4 * i) = make_float4(gu, gv, 0.f, 0.f);
+}
+
+// interpolate with the pixel derivatives of a LIST of channels: out_da [npix][2 nidx], pair k = (d attr[idx[k]] / dX, d attr[idx[k]] / dY)
+// (idx NULL: every channel in order, nidx = na -- interp_fwd_kernel's out_da)
+__global__ __launch_bounds__(256) void interp_fwd_da_kernel(const float* __restrict__ attr, int attr_bstride, int na, const float* __restrict__ rast,
+                                                            const int* __restrict__ tri, const float* __restrict__ db, const int* __restrict__ idx,
+                                                            int nidx, size_t npix_total, size_t npix_per_b, float* __restrict__ out,
+                                                            float* __restrict__ out_da) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix_total) return;
+    float4 r = *(const float4*)(rast + 4 * i);
+    int id = (int)r.w;
+    float* o = out + i * na;
+    float* od = out_da + i * 2 * nidx;
+    if (id <= 0) {
+        for (int c = 0; c < na; ++c) o[c] = 0.f;
+        for (int c = 0; c < 2 * nidx; ++c) od[c] = 0.f;
+        return;
+    }
+    int b = (int)(i / npix_per_b);
+    const float* ab = attr + (size_t)b * attr_bstride;
+    int f = id - 1;
+    const float* a0 = ab + (size_t)tri[3 * (size_t)f] * na;
+    const float* a1 = ab + (size_t)tri[3 * (size_t)f + 1] * na;
+    const float* a2 = ab + (size_t)tri[3 * (size_t)f + 2] * na;
+    float u = r.x, v = r.y, w = 1.0f - u - v;
+    for (int c = 0; c < na; ++c) o[c] = u * a0[c] + v * a1[c] + w * a2[c];
+    const float4 d = *(const float4*)(db + 4 * i);
+    for (int k = 0; k < nidx; ++k) {
+        const int c = idx ? idx[k] : k;
+        float x2 = a2[c], e0 = a0[c] - x2, e1 = a1[c] - x2;
+        od[2 * k + 0] = d.x * e0 + d.z * e1;
+        od[2 * k + 1] = d.y * e0 + d.w * e1;
+    }
+}
+
+// interpolate backward with the adjoint of the attribute pixel derivatives.  Per listed channel c = idx[k] (e0 = a0 - a2, e1 = a1 - a2 and
+// (gX, gY) = g_da[2k], g_da[2k+1]): d a0 += gX db.x + gY db.y, d a1 += gX db.z + gY db.w, d a2 -= both, and d_db += (gX e0, gY e0, gX e1,
+// gY e1).  g_out (may be NULL) goes as in interp_bwd_kernel; out_da does not depend on (u, v), so d_rast carries g_out's part only.  Runs of
+// lanes on one triangle are reduced before the attribute atomics, as there.  idx NULL: every channel in order (nidx = na), folded into the
+// g_out loop (one atomic per run, vertex and channel).
+__global__ __launch_bounds__(256) void interp_bwd_da_kernel(const float* __restrict__ attr, int attr_bstride, int na, const float* __restrict__ rast,
+                                                            const int* __restrict__ tri, const float* __restrict__ db, const int* __restrict__ idx,
+                                                            int nidx, const float* __restrict__ g_out, const float* __restrict__ g_da,
+                                                            size_t npix_total, size_t npix_per_b, float* __restrict__ d_attr,
+                                                            float* __restrict__ d_rast, float* __restrict__ d_db) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool inb = i < npix_total;
+    float4 r = inb ? *(const float4*)(rast + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int id = (int)r.w;
+    const bool hit = id > 0;
+    if (__ballot(hit) == 0ull) {            // wave-uniform: nothing covered here
+        if (d_rast && inb) *(float4*)(d_rast + 4 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (d_db && inb) *(float4*)(d_db + 4 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int b = inb ? (int)(i / npix_per_b) : 0;
+    const D3hSeg sg = d3h_seg_runs(hit ? id + (b << 24) : -1, lane);
+    size_t i0 = 0, i1 = 0, i2 = 0;
+    if (hit) {
+        int f = id - 1;
+        i0 = (size_t)tri[3 * (size_t)f] * na; i1 = (size_t)tri[3 * (size_t)f + 1] * na; i2 = (size_t)tri[3 * (size_t)f + 2] * na;
+    }
+    const float* ab = attr + (size_t)b * attr_bstride;
+    float* dab = d_attr ? d_attr + (size_t)b * attr_bstride : nullptr;
+    const float u = r.x, v = r.y;
+    const float4 d = (hit && g_da) ? *(const float4*)(db + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float gu = 0.f, gv = 0.f;
+    float4 gd = make_float4(0.f, 0.f, 0.f, 0.f);
+    // per channel c: g_out part (when given), and the g_da part of channel c itself when the list is every channel (idx NULL)
+    const bool fold = !idx && g_da;
+    for (int c = 0; c < ((g_out || fold) ? na : 0); ++c) {
+        const float gc = (hit && g_out) ? g_out[i * na + c] : 0.f;
+        const float gX = (hit && fold) ? g_da[i * 2 * nidx + 2 * c] : 0.f, gY = (hit && fold) ? g_da[i * 2 * nidx + 2 * c + 1] : 0.f;
+        const float p = gX * d.x + gY * d.y, q = gX * d.z + gY * d.w;
+        if (dab) {
+            float s0 = d3h_seg_sum(gc * u + p, lane, sg.start);
+            float s1 = d3h_seg_sum(gc * v + q, lane, sg.start);
+            float s2 = d3h_seg_sum(gc * (1.0f - u - v) - (p + q), lane, sg.start);
+            if (sg.tail && hit) {
+                if (s0 != 0.f) atomicAdd(dab + i0 + c, s0);
+                if (s1 != 0.f) atomicAdd(dab + i1 + c, s1);
+                if (s2 != 0.f) atomicAdd(dab + i2 + c, s2);
+            }
+        }
+        if (hit && (gc != 0.f || gX != 0.f || gY != 0.f)) {
+            float x2 = ab[i2 + c], e0 = ab[i0 + c] - x2, e1 = ab[i1 + c] - x2;
+            gu = fmaf(gc, e0, gu);
+            gv = fmaf(gc, e1, gv);
+            gd.x = fmaf(gX, e0, gd.x); gd.y = fmaf(gY, e0, gd.y); gd.z = fmaf(gX, e1, gd.z); gd.w = fmaf(gY, e1, gd.w);
+        }
+    }
+    // a list of channels (in any order, repeats allowed): one pass over the list
+    for (int k = 0; k < ((idx && g_da) ? nidx : 0); ++k) {
+        const int c = idx[k];
+        const float gX = hit ? g_da[i * 2 * nidx + 2 * k] : 0.f, gY = hit ? g_da[i * 2 * nidx + 2 * k + 1] : 0.f;
+        const float p = gX * d.x + gY * d.y, q = gX * d.z + gY * d.w;
+        if (dab) {
+            float s0 = d3h_seg_sum(p, lane, sg.start);
+            float s1 = d3h_seg_sum(q, lane, sg.start);
+            float s2 = d3h_seg_sum(-(p + q), lane, sg.start);
+            if (sg.tail && hit) {
+                if (s0 != 0.f) atomicAdd(dab + i0 + c, s0);
+                if (s1 != 0.f) atomicAdd(dab + i1 + c, s1);
+                if (s2 != 0.f) atomicAdd(dab + i2 + c, s2);
+            }
+        }
+        if (hit && (gX != 0.f || gY != 0.f)) {
+            float x2 = ab[i2 + c], e0 = ab[i0 + c] - x2, e1 = ab[i1 + c] - x2;
+            gd.x = fmaf(gX, e0, gd.x); gd.y = fmaf(gY, e0, gd.y); gd.z = fmaf(gX, e1, gd.z); gd.w = fmaf(gY, e1, gd.w);
+        }
+    }
+    if (d_rast && inb) *(float4*)(d_rast + 4 * i) = make_float4(gu, gv, 0.f, 0.f);
+    if (d_db && inb) *(float4*)(d_db + 4 * i) = gd;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1391,6 +1581,19 @@ extern "C" int d3h_rasterize_bwd(const float* pos, int pos_bstride, const int* t
     return D3H_OK;
 }
 
+// d3h_rasterize_bwd with the gradient of the pixel derivatives: g_rast [nb][H][W][4] (d(u, v); may be NULL) and g_db [nb][H][W][4]
+// (d(du/dX, du/dY, dv/dX, dv/dY); may be NULL) -> d_pos, accumulated (caller zero-fills)
+extern "C" int d3h_rasterize_bwd_db(const float* pos, int pos_bstride, const int* tri, int nb, int H, int W, const float* rast,
+                                    const float* g_rast, const float* g_db, float* d_pos, void* stream) {
+    if (nb < 0 || H < 0 || W < 0 || !d_pos) return D3H_ERR_ARG;
+    size_t npix = (size_t)nb * H * W;
+    if (npix == 0 || (!g_rast && !g_db)) return D3H_OK;
+    hipLaunchKernelGGL(raster_bwd_db_kernel, dim3(d3h_cdiv(npix, 256)), dim3(256), 0, (hipStream_t)stream, pos, pos_bstride, tri, H, W, nb, rast,
+                       g_rast, g_db, d_pos);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
 // attr [nb or 1][nv][na] (attr_bstride = nv*na or 0); out [nb][H][W][na]; out_da [nb][H][W][2 na] (optional, needs db)
 extern "C" int d3h_interpolate_fwd(const float* attr, int attr_bstride, int na, const float* rast, const int* tri, const float* db, int nb,
                                    int H, int W, float* out, float* out_da, void* stream) {
@@ -1409,6 +1612,37 @@ extern "C" int d3h_interpolate_bwd(const float* attr, int attr_bstride, int na, 
     if (n == 0) return D3H_OK;
     hipLaunchKernelGGL(interp_bwd_kernel, dim3(d3h_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attr, attr_bstride, na, rast, tri, g_out, n,
                        npb, d_attr, d_rast);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// d3h_interpolate_fwd with the pixel derivatives of a list of channels: idx [nidx] int32, each in [0, na) (NULL: every channel in order,
+// nidx = na); out [nb][H][W][na] and out_da [nb][H][W][2 nidx] overwritten, pair k = (d attr[idx[k]] / dX, d attr[idx[k]] / dY) from
+// db [nb][H][W][4]
+extern "C" int d3h_interpolate_fwd_da(const float* attr, int attr_bstride, int na, const float* rast, const int* tri, const float* db,
+                                      const int* idx, int nidx, int nb, int H, int W, float* out, float* out_da, void* stream) {
+    if (nb < 0 || H < 0 || W < 0 || na < 0 || nidx < 0 || (!idx && nidx != na)) return D3H_ERR_ARG;
+    size_t npb = (size_t)H * W, n = npb * nb;
+    if (n == 0) return D3H_OK;
+    if (!rast || !out || !out_da || !db) return D3H_ERR_ARG;
+    hipLaunchKernelGGL(interp_fwd_da_kernel, dim3(d3h_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attr, attr_bstride, na, rast, tri, db,
+                       idx, nidx, n, npb, out, out_da);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// d3h_interpolate_bwd with the gradient of the attribute pixel derivatives: g_out [nb][H][W][na] (may be NULL), g_da [nb][H][W][2 nidx]
+// (may be NULL; needs db) for the channels idx [nidx] of d3h_interpolate_fwd_da (NULL: every channel, nidx = na).  d_attr accumulated
+// (caller zero-fills; may be NULL); d_rast [nb][H][W][4] and d_db [nb][H][W][4] overwritten, zero where nothing is covered (may be NULL)
+extern "C" int d3h_interpolate_bwd_da(const float* attr, int attr_bstride, int na, const float* rast, const int* tri, const float* db,
+                                      const int* idx, int nidx, const float* g_out, const float* g_da, int nb, int H, int W, float* d_attr,
+                                      float* d_rast, float* d_db, void* stream) {
+    if (nb < 0 || H < 0 || W < 0 || na < 0 || nidx < 0 || (!idx && nidx != na) || (g_da && !db)) return D3H_ERR_ARG;
+    size_t npb = (size_t)H * W, n = npb * nb;
+    if (n == 0) return D3H_OK;
+    if (!rast) return D3H_ERR_ARG;
+    hipLaunchKernelGGL(interp_bwd_da_kernel, dim3(d3h_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attr, attr_bstride, na, rast, tri, db,
+                       idx, nidx, g_out, g_da, n, npb, d_attr, d_rast, d_db);
     D3H_LAUNCH_CHECK();
     return D3H_OK;
 }

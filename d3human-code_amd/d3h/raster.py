@@ -2,6 +2,16 @@
 
 Signatures follow nvdiffrast.torch as the reference calls it (render/render.py:37,72,102,381,400-403); the shim module
 `nvdiffrast/torch.py` re-exports these.  Tensors: pos [B or 1, V, 4] clip space, tri [F,3] int32, images NHWC float32.
+
+Pixel derivatives (nvdiffrast is not vendored; this paragraph is the pin of what is differentiated):
+  - rasterize(grad_db=True): rast_db = (du/dX, du/dY, dv/dX, dv/dY) in pixel units is differentiable in pos.  Per covered pixel it is the
+    closed form of csrc/raster.hip:resolve_pixel at the pixel's winning triangle, a function of that triangle's X_k = x_k/w_k, Y_k = y_k/w_k,
+    q_k = 1/w_k and the pixel centre; its exact adjoint is added to the barycentric one.  The winner itself (the visibility decision) and
+    empty pixels carry no gradient, as for rast.  grad_db=False (this module's default): rast_db is returned but is not differentiable.
+  - interpolate(rast_db=..., diff_attrs='all' | [indices]): out_da [.., 2 len(diff_attrs)] = per listed channel c, in list order,
+    (dA_c/dX, dA_c/dY) = (db.x e0 + db.z e1, db.y e0 + db.w e1), e0 = a0 - a2, e1 = a1 - a2.  It is differentiable in attr and rast_db,
+    never in rast: out_da does not depend on (u, v).  Zero where nothing is covered, and so is its gradient.
+  - Not covered: ranges (range mode), depth peeling beyond the first layer, antialias's topology_hash / pos_gradient_boost.
 """
 import os
 import torch
@@ -39,7 +49,7 @@ class _Scratch:
 
 class _RasterizeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pos, tri, H, W, nb, want_db=True):
+    def forward(ctx, pos, tri, H, W, nb, want_db=True, grad_db=False):
         lib = L.lib()
         pos_c = pos.contiguous().float()
         dev = pos.device
@@ -59,72 +69,105 @@ class _RasterizeFn(torch.autograd.Function):
                                       L.ptr(zbuf), L.ptr(big), L.i32(big_cap), L.ptr(rast), L.ptr(db if want_db else None), L.stream()), 'rasterize_fwd')
         ctx.save_for_backward(pos_c, tri, rast)
         ctx.dims = (H, W, nb)
-        ctx.mark_non_differentiable(db)
+        if not (grad_db and want_db):
+            ctx.mark_non_differentiable(db)
         # (without this the engine hands the backward a zero-filled [nb, H, W, 4] tensor for `db` on every step: a 67 MB fill nobody reads)
         ctx.set_materialize_grads(False)
         ctx.zeros = L.zeros_like(pos) if ctx.needs_input_grad[0] else None      # d_pos, filled ahead of the backward (d3h/mtets.py)
         return rast, db
 
     @staticmethod
-    def backward(ctx, g_rast, _g_db):
+    def backward(ctx, g_rast, g_db):
         pos, tri, rast = ctx.saved_tensors
         H, W, nb = ctx.dims
         d_pos, ctx.zeros = getattr(ctx, 'zeros', None), None
         if d_pos is None:
             d_pos = L.zeros_like(pos)
+        if g_db is not None:                   # the pixel derivatives were differentiated: one pass for both gradients
+            L.check(L.lib().d3h_rasterize_bwd_db(L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rast),
+                                                 L.ptr(g_rast.contiguous() if g_rast is not None else None), L.ptr(g_db.contiguous()),
+                                                 L.ptr(d_pos), L.stream()), 'rasterize_bwd_db')
+            return d_pos, None, None, None, None, None, None
         if g_rast is None:                     # nothing flowed into the barycentrics: the position gradient through them is zero
-            return d_pos, None, None, None, None, None
+            return d_pos, None, None, None, None, None, None
         L.check(L.lib().d3h_rasterize_bwd(L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rast),
                                           L.ptr(g_rast.contiguous()), L.ptr(d_pos), L.stream()), 'rasterize_bwd')
-        return d_pos, None, None, None, None, None
+        return d_pos, None, None, None, None, None, None
 
 
-def rasterize(pos, tri, resolution, nb=None, want_db=True):
-    """-> (rast [B,H,W,4] = (u, v, z/w, tri_id+1), rast_db [B,H,W,4] = (du/dX, du/dY, dv/dX, dv/dY); want_db False (extension): rast_db is None)"""
+def rasterize(pos, tri, resolution, nb=None, want_db=True, grad_db=False):
+    """-> (rast [B,H,W,4] = (u, v, z/w, tri_id+1), rast_db [B,H,W,4] = (du/dX, du/dY, dv/dX, dv/dY); want_db False (extension): rast_db is None).
+    grad_db True: rast_db is differentiable in pos (module docstring); False: it is returned without a gradient."""
     H, W = int(resolution[0]), int(resolution[1])
     nb = pos.shape[0] if nb is None else nb
-    rast, db = _RasterizeFn.apply(pos, tri.contiguous(), H, W, nb, bool(want_db))
+    rast, db = _RasterizeFn.apply(pos, tri.contiguous(), H, W, nb, bool(want_db), bool(grad_db))
     return rast, (db if want_db else None)
 
 
 class _InterpolateFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, attr, rast, tri, rast_db):
+    def forward(ctx, attr, rast, tri, rast_db, diff_idx):
         lib = L.lib()
         attr_c = attr.contiguous().float()
         rast_c = rast.contiguous()
         nb, H, W = rast_c.shape[:3]
         na = attr_c.shape[2]
+        db_c = rast_db.contiguous().float() if rast_db is not None else None
         out = torch.empty(nb, H, W, na, dtype=torch.float32, device=attr.device)
-        out_da = torch.empty(nb, H, W, 2 * na, dtype=torch.float32, device=attr.device) if rast_db is not None else None
-        L.check(lib.d3h_interpolate_fwd(L.ptr(attr_c), L.i32(_bstride(attr_c)), L.i32(na), L.ptr(rast_c), L.ptr(tri),
-                                        L.ptr(rast_db.contiguous() if rast_db is not None else None), L.i32(nb), L.i32(H), L.i32(W),
-                                        L.ptr(out), L.ptr(out_da), L.stream()), 'interpolate_fwd')
-        ctx.save_for_backward(attr_c, rast_c, tri)
+        if diff_idx is None:                   # no derivatives, or every channel in order
+            out_da = torch.empty(nb, H, W, 2 * na, dtype=torch.float32, device=attr.device) if rast_db is not None else None
+            L.check(lib.d3h_interpolate_fwd(L.ptr(attr_c), L.i32(_bstride(attr_c)), L.i32(na), L.ptr(rast_c), L.ptr(tri), L.ptr(db_c),
+                                            L.i32(nb), L.i32(H), L.i32(W), L.ptr(out), L.ptr(out_da), L.stream()), 'interpolate_fwd')
+        else:
+            out_da = torch.empty(nb, H, W, 2 * diff_idx.numel(), dtype=torch.float32, device=attr.device)
+            L.check(lib.d3h_interpolate_fwd_da(L.ptr(attr_c), L.i32(_bstride(attr_c)), L.i32(na), L.ptr(rast_c), L.ptr(tri), L.ptr(db_c),
+                                               L.ptr(diff_idx), L.i32(diff_idx.numel()), L.i32(nb), L.i32(H), L.i32(W), L.ptr(out), L.ptr(out_da),
+                                               L.stream()), 'interpolate_fwd_da')
+        ctx.save_for_backward(attr_c, rast_c, tri, db_c, diff_idx)
         if out_da is None:
             out_da = out.new_empty(0)
-        ctx.mark_non_differentiable(out_da)
+            ctx.mark_non_differentiable(out_da)
+        ctx.set_materialize_grads(False)
         return out, out_da
 
     @staticmethod
-    def backward(ctx, g_out, _g_da):
-        attr, rast, tri = ctx.saved_tensors
+    def backward(ctx, g_out, g_da):
+        attr, rast, tri, db, diff_idx = ctx.saved_tensors
         nb, H, W = rast.shape[:3]
         na = attr.shape[2]
-        need_attr, need_rast = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_attr, need_rast, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if g_da is None and g_out is None:
+            return None, None, None, None, None
         d_attr = L.zeros_like(attr) if need_attr else None
         d_rast = torch.empty_like(rast) if need_rast else None
-        L.check(L.lib().d3h_interpolate_bwd(L.ptr(attr), L.i32(_bstride(attr)), L.i32(na), L.ptr(rast), L.ptr(tri), L.ptr(g_out.contiguous()),
-                                            L.i32(nb), L.i32(H), L.i32(W), L.ptr(d_attr), L.ptr(d_rast), L.stream()), 'interpolate_bwd')
-        return d_attr, d_rast, None, None
+        if g_da is None:
+            L.check(L.lib().d3h_interpolate_bwd(L.ptr(attr), L.i32(_bstride(attr)), L.i32(na), L.ptr(rast), L.ptr(tri), L.ptr(g_out.contiguous()),
+                                                L.i32(nb), L.i32(H), L.i32(W), L.ptr(d_attr), L.ptr(d_rast), L.stream()), 'interpolate_bwd')
+            return d_attr, d_rast, None, None, None
+        d_db = torch.empty_like(db) if need_db else None
+        nidx = na if diff_idx is None else diff_idx.numel()
+        L.check(L.lib().d3h_interpolate_bwd_da(L.ptr(attr), L.i32(_bstride(attr)), L.i32(na), L.ptr(rast), L.ptr(tri), L.ptr(db), L.ptr(diff_idx),
+                                               L.i32(nidx), L.ptr(g_out.contiguous() if g_out is not None else None), L.ptr(g_da.contiguous()),
+                                               L.i32(nb), L.i32(H), L.i32(W), L.ptr(d_attr), L.ptr(d_rast), L.ptr(d_db), L.stream()), 'interpolate_bwd_da')
+        return d_attr, d_rast, None, d_db, None
 
 
 def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
-    """nvdiffrast.interpolate: (out [B,H,W,A], out_da [B,H,W,2A] or empty).  The attribute pixel derivatives are
-    forward-only: the reference only evaluates them under no_grad (render/render.py:291-299)."""
+    """nvdiffrast.interpolate: (out [B,H,W,A], out_da [B,H,W,2 len(diff_attrs)] or None).  diff_attrs: None, 'all' or a list of channel
+    indices (their derivatives in list order); out_da is produced only with rast_db and is differentiable in attr and rast_db (module
+    docstring)."""
     if attr.dim() == 2:
         attr = attr[None]
-    out, da = _InterpolateFn.apply(attr, rast, tri.contiguous(), rast_db if diff_attrs is not None else None)
+    idx = None
+    if diff_attrs is not None and rast_db is not None and not (isinstance(diff_attrs, str) and diff_attrs == 'all'):
+        if isinstance(diff_attrs, str):
+            raise ValueError(f"interpolate: diff_attrs must be None, 'all' or a list of channel indices, not {diff_attrs!r}")
+        lst = [int(c) for c in diff_attrs]
+        na = attr.shape[-1]
+        if any(not 0 <= c < na for c in lst):
+            raise ValueError(f'interpolate: diff_attrs {lst} out of range for {na} attribute channels')
+        idx = torch.tensor(lst, dtype=torch.int32).to(attr.device)
+    out, da = _InterpolateFn.apply(attr, rast, tri.contiguous(), rast_db if diff_attrs is not None else None, idx)
     return out, (da if da.numel() else None)
 
 

@@ -15,13 +15,15 @@ RasterizeCudaContext = RasterizeGLContext
 
 
 def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
-    return _rasterize(pos, tri, resolution)
+    """nvdiffrast's defaults: with grad_db (the default) the pixel derivatives are differentiable in pos; without, they come back detached"""
+    return _rasterize(pos, tri, resolution, grad_db=grad_db)
 
 
 class DepthPeeler:
-    """render/render.py:400-403 uses exactly one layer; the first layer is a plain rasterize"""
-    def __init__(self, glctx, pos, tri, resolution):
+    """render/render.py:400-403 uses exactly one layer; the first layer is a plain rasterize (grad_db as in rasterize)"""
+    def __init__(self, glctx, pos, tri, resolution, ranges=None, grad_db=True):
         self.pos, self.tri, self.res = pos, tri, resolution
+        self.grad_db = grad_db
         self.layer = 0
 
     def __enter__(self):
@@ -35,7 +37,7 @@ class DepthPeeler:
         if self.layer > 0:
             raise NotImplementedError('d3h DepthPeeler: only the first layer (the reference asserts num_layers == 1)')
         self.layer += 1
-        return _rasterize(self.pos, self.tri, self.res, want_db=want_db)
+        return _rasterize(self.pos, self.tri, self.res, want_db=want_db, grad_db=self.grad_db)
 
 
 def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='auto', boundary_mode='wrap', max_mip_level=None):

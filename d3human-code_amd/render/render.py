@@ -205,7 +205,8 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     # the pixel derivatives of the barycentrics are read by the z-gradient pass only (render.py:291-299): not written when no buffer wants it
     no_grad_of = lambda k: k in want and (not grad_on or (live is not None and k not in live))
     need_aux = 'z_grad' in want or no_grad_of('depth') or no_grad_of('invdepth')
-    with dr.DepthPeeler(ctx, v_pos_clip, tri, [Hf, Wf]) as peeler:
+    # grad_db=False: db feeds the no-grad z-gradient pass only, so its (spp > 1) rescale below records no autograd node
+    with dr.DepthPeeler(ctx, v_pos_clip, tri, [Hf, Wf], grad_db=False) as peeler:
         rast_full, db_full = peeler.rasterize_next_layer(want_db='z_grad' in want)
     rast, db = rast_full, db_full
     if spp > 1 and msaa:                          # shade at the framebuffer resolution (render.py:241-245): nearest sample of the raster
