@@ -205,6 +205,91 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
+// depth peeling and range mode (the contract: d3h/raster.py's docstring)
+// ------------------------------------------------------------------------------------------------
+// Previous-layer keys, one thread per pixel: the (depth | id) key the previous layer's winner (rast.w) had at this pixel, RECOMPUTED with the
+// device functions that chose it -- load_tri, then raster_key_cross, or tri_bbox's area and raster_key -- so it is the same arithmetic and the
+// same bits as the key that won.  An empty pixel gets ~0 (nothing is admitted there any more), and so does an id outside [1, nf] or a key that
+// does not recompute (neither can come from a layer of these pos / tri).  16 B read + 8 B written per pixel; no z-buffer is kept between layers.
+__global__ __launch_bounds__(256) void raster_peel_key_kernel(const float* __restrict__ pos, int pos_bstride, const int* __restrict__ tri, int nf,
+                                                              int H, int W, int nb, const float* __restrict__ prev_rast,
+                                                              unsigned long long* __restrict__ prev_key) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    size_t n = (size_t)nb * H * W;
+    if (i >= n) return;
+    const float4 r = *(const float4*)(prev_rast + 4 * i);
+    const int id = (int)r.w;
+    unsigned long long key = ~0ull;
+    if (id > 0 && id <= nf) {
+        const int b = (int)(i / ((size_t)H * W));
+        const int rem = (int)(i % ((size_t)H * W));
+        const int px = rem % W, py = rem / W, f = id - 1;
+        TriSetup t = load_tri(pos + (size_t)b * pos_bstride, tri, f);
+        unsigned long long k;
+        float area;
+        int x0, x1, y0, y1;
+        const bool ok = t.cross ? raster_key_cross(t, px, py, W, H, f, k)
+                                : (t.ok && tri_bbox(t, W, H, area, x0, x1, y0, y1) && raster_key(t, area, px, py, W, H, f, k));
+        if (ok) key = k;
+    }
+    prev_key[i] = key;
+}
+
+// raster_tris_kernel for a peeled layer and / or range mode (the wave path only; the tile-binned kernel is never used here).
+//  - prev_key [nb][H][W] (or NULL): a fragment enters the atomicMin only if its key is STRICTLY greater than the previous layer's key at that
+//    pixel; a lane reads its previous key only where the pixel is covered, so the 8 x 8 block reads them one 64-B row at a time.
+//  - ranges [nb][2] = (start, count) (or NULL): frame b rasterises triangles start .. start + count - 1 of tri (the grid's x dimension is
+//    sized by the largest count; the ids stay absolute); pos is then shared by every frame (pos_bstride = 0).  A range outside [0, nf]
+//    rasterises nothing (the host refuses it before the launch).
+__global__ __launch_bounds__(256) void raster_tris_peel_kernel(const float* __restrict__ pos, int pos_bstride, const int* __restrict__ tri, int nf,
+                                                               const int* __restrict__ ranges, int H, int W,
+                                                               const unsigned long long* __restrict__ prev_key, unsigned long long* __restrict__ zbuf) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = blockIdx.y;
+    int start = 0, count = nf;
+    if (ranges) {
+        start = ranges[2 * b];
+        count = ranges[2 * b + 1];
+        if (start < 0 || count < 0 || start > nf - count) return;
+    }
+    const int local = (blockIdx.x * 4 + wave) * TRIS_PER_WAVE;
+    const float* posb = pos + (size_t)b * pos_bstride;
+    unsigned long long* zb = zbuf + (size_t)b * H * W;
+    const unsigned long long* pk = prev_key ? prev_key + (size_t)b * H * W : nullptr;
+    const int lx = lane & 7, ly = lane >> 3;
+    const int fend = start + min(local + TRIS_PER_WAVE, count);
+    for (int f = start + local; f < fend; ++f) {
+        TriSetup t = load_tri(posb, tri, f);
+        if (t.cross) {                          // rare: the whole frame is its bounding box
+            for (int by = 0; by < H; by += 8)
+                for (int bx = 0; bx < W; bx += 8) {
+                    int px = bx + lx, py = by + ly;
+                    unsigned long long key;
+                    if (px < W && py < H && raster_key_cross(t, px, py, W, H, f, key)) {
+                        const size_t o = (size_t)py * W + px;
+                        if (!pk || key > pk[o]) atomicMin(&zb[o], key);
+                    }
+                }
+            continue;
+        }
+        if (!t.ok) continue;                    // entirely behind the camera plane
+        float area;
+        int x0, x1, y0, y1;
+        if (!tri_bbox(t, W, H, area, x0, x1, y0, y1)) continue;
+        for (int by = y0; by <= y1; by += 8)
+            for (int bx = x0; bx <= x1; bx += 8) {
+                int px = bx + lx, py = by + ly;
+                unsigned long long key;
+                if (px <= x1 && py <= y1 && raster_key(t, area, px, py, W, H, f, key)) {
+                    const size_t o = (size_t)py * W + px;
+                    if (!pk || key > pk[o]) atomicMin(&zb[o], key);
+                }
+            }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // tile-binned rasteriser (large meshes)
 // ------------------------------------------------------------------------------------------------
 // The wave-per-triangle kernel above is right for the fitted meshes of this workload (~10^4 triangles of 10^2..10^3 pixels: 69 us for four
@@ -1565,6 +1650,49 @@ extern "C" int d3h_rasterize_fwd(const float* pos, int nv, int pos_bstride, cons
         hipLaunchKernelGGL(raster_tris_kernel, dim3(d3h_cdiv(nf, 4 * TRIS_PER_WAVE), nb), dim3(256), 0, s, pos, nv, pos_bstride, tri, nf, H, W, zbuf, flag);
     hipLaunchKernelGGL(raster_resolve_kernel, dim3(d3h_cdiv(npix, 256)), dim3(256), 0, s, pos, pos_bstride, tri, H, W, nb, zbuf, rast, db, flag);
     d3h_ktime_end(kt_, (hipStream_t)(stream));
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// Depth peeling, first half: prev_key [nb][H][W] uint64 (overwritten; caller-owned scratch) = the (depth | id) key that the winner recorded in
+// prev_rast [nb][H][W][4] -- a layer d3h_rasterize_fwd or d3h_rasterize_peel_fwd rendered from these pos / tri -- has at each pixel; ~0 where
+// that layer is empty.  The same arithmetic as the rasteriser's, so the keys are bit-identical to the ones that won.
+extern "C" int d3h_rasterize_peel_keys(const float* pos, int pos_bstride, const int* tri, int nf, int nb, int H, int W, const float* prev_rast,
+                                       unsigned long long* prev_key, void* stream) {
+    if (nb < 0 || H < 0 || W < 0 || nf < 0 || !prev_rast || !prev_key) return D3H_ERR_ARG;
+    size_t npix = (size_t)nb * H * W;
+    if (npix == 0) return D3H_OK;
+    hipLaunchKernelGGL(raster_peel_key_kernel, dim3(d3h_cdiv(npix, 256)), dim3(256), 0, (hipStream_t)stream, pos, pos_bstride, tri, nf, H, W, nb,
+                       prev_rast, prev_key);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// One layer of depth peeling and / or range mode, on the wave-per-triangle rasteriser; writes rast / db as d3h_rasterize_fwd (db may be NULL).
+//  - prev_rast (or NULL): the previous layer.  Its keys go to prev_key [nb][H][W] uint64 (caller-owned scratch; d3h_rasterize_peel_keys) and
+//    each pixel then reports the covering fragment with the smallest key strictly greater than its previous key.  prev_rast NULL and
+//    prev_key non-NULL: prev_key already holds those keys.  Both NULL: no peeling (the first layer).
+//  - ranges [nb][2] int32 (device; or NULL) = (start, count) into tri per frame: range mode.  pos is [nv][4], shared (pos_bstride must be 0),
+//    max_count >= every count (it sizes the grid), and every range lies inside [0, nf] -- a range outside it rasterises nothing.  The ids in
+//    rast are absolute (tri index + 1).  ranges NULL: the frames rasterise all nf triangles, max_count is ignored.
+//  zbuf: nb*H*W uint64 scratch.  The backward of every layer is d3h_rasterize_bwd / d3h_rasterize_bwd_db with the same pos_bstride.
+extern "C" int d3h_rasterize_peel_fwd(const float* pos, int pos_bstride, const int* tri, int nf, int nb, int H, int W, const int* ranges,
+                                      int max_count, const float* prev_rast, unsigned long long* prev_key, unsigned long long* zbuf, float* rast,
+                                      float* db, void* stream) {
+    if (nb <= 0 || H <= 0 || W <= 0 || nf < 0 || !rast || !zbuf) return D3H_ERR_ARG;
+    if (ranges && (pos_bstride != 0 || max_count < 0 || max_count > nf)) return D3H_ERR_ARG;
+    if (prev_rast && !prev_key) return D3H_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    size_t npix = (size_t)nb * H * W;
+    if (prev_rast)
+        hipLaunchKernelGGL(raster_peel_key_kernel, dim3(d3h_cdiv(npix, 256)), dim3(256), 0, s, pos, pos_bstride, tri, nf, H, W, nb, prev_rast, prev_key);
+    (void)hipMemsetAsync(zbuf, 0xFF, npix * 8, s);
+    const int ntri = ranges ? max_count : nf;
+    if (ntri > 0)
+        hipLaunchKernelGGL(raster_tris_peel_kernel, dim3(d3h_cdiv(ntri, 4 * TRIS_PER_WAVE), nb), dim3(256), 0, s, pos, pos_bstride, tri, nf, ranges, H, W,
+                           (const unsigned long long*)prev_key, zbuf);
+    hipLaunchKernelGGL(raster_resolve_kernel, dim3(d3h_cdiv(npix, 256)), dim3(256), 0, s, pos, pos_bstride, tri, H, W, nb, (const unsigned long long*)zbuf,
+                       rast, db, (const int*)nullptr);
     D3H_LAUNCH_CHECK();
     return D3H_OK;
 }

@@ -11,7 +11,37 @@ Pixel derivatives (nvdiffrast is not vendored; this paragraph is the pin of what
   - interpolate(rast_db=..., diff_attrs='all' | [indices]): out_da [.., 2 len(diff_attrs)] = per listed channel c, in list order,
     (dA_c/dX, dA_c/dY) = (db.x e0 + db.z e1, db.y e0 + db.w e1), e0 = a0 - a2, e1 = a1 - a2.  It is differentiable in attr and rast_db,
     never in rast: out_da does not depend on (u, v).  Zero where nothing is covered, and so is its gradient.
-  - Not covered: ranges (range mode), depth peeling beyond the first layer, antialias's topology_hash / pos_gradient_boost.
+
+Depth peeling (rasterize(prev_rast=...); nvdiffrast.torch.DepthPeeler):
+  - The key of a fragment is the rasteriser's 64-bit (order_key(z/w) << 32) | (id + 1) (csrc/raster.hip: raster_key / raster_key_cross).
+    Layer k reports, at each pixel, the covering fragment whose key is the SMALLEST KEY STRICTLY GREATER than the key layer k-1 reported
+    there; a fragment covers under the same coverage, near-plane and depth-range tests as rasterize.  A pixel with no such fragment is
+    empty (all four channels zero) and stays empty in every later layer.  So every fragment layer 0 competes over appears in exactly one
+    layer, in increasing (depth, id) order.
+  - Ties (this build's rule): fragments with equal z/w -- a duplicated or coplanar triangle -- are ALL reported, one per layer, in id order.
+  - Layer 0 is rasterize bit for bit (DepthPeeler's first call is a plain rasterize: the same entry point and cost).  Every layer's rast
+    and db are differentiable exactly as layer 0's, under the same grad_db / want_db rules: through that layer's winning triangle; the
+    visibility decision carries no gradient.
+  - How: a previous-key pass recomputes, per pixel, the key the previous layer's winner (rast.w) had there with the same device functions,
+    so bit-identical to the key that won (no z-buffer is kept between layers), then the wave-per-triangle rasteriser admits a fragment to
+    its atomic-min only above that key.  Peeled layers always take the wave path, never the tile-binned one (BIN_MIN_TRIS).
+  - DepthPeeler keeps the previous layer's rast and refuses (RuntimeError) to peel from it once it was modified in place; after the last
+    non-empty layer it returns empty layers, as nvdiffrast's fixed-count loop expects.
+
+Range mode (rasterize(pos [V,4], ranges=...), nvdiffrast's):
+  - ranges: an int32 CPU tensor [B,2] of (start, count) into tri; frame b rasterises triangles start_b .. start_b + count_b - 1 and rast is
+    [B,H,W,4].  Ids in rast are ABSOLUTE indices into tri, plus one, so interpolate (2-D attr) and antialias (2-D pos) take the whole tri.
+    Each frame equals the instanced rasterize(pos[None], tri[start:start + count]) with its ids offset by start, bit for bit (rast and db);
+    d_pos comes back [V,4], summed over the frames.  Peeling works in range mode too.  Range mode takes the wave path only.
+  - A 2-D pos without ranges, ranges that are not an int32 CPU [B,2] tensor (B >= 1), a negative start or count, or a range past F raise
+    ValueError.  With a 3-D pos, ranges is ignored (instanced mode), as in nvdiffrast.
+
+Antialias options:
+  - pos may be 2-D [V,4] (range mode: shared by every frame); silhouettes come from the topology of the whole tri, as nvdiffrast's hash.
+  - pos_gradient_boost: d_pos is multiplied by it; the colour gradient is unchanged.
+  - topology_hash = antialias_construct_topology_hash(tri): the edge hash built once in buffers of its own and reused; results are
+    bit-identical to calling without it.  A hash built for another triangle count raises ValueError.
+  - Not covered: OpenGL-only options of nvdiffrast; layered compositing of peeled layers in render/render.py (it asserts num_layers == 1).
 """
 import os
 import torch
@@ -49,7 +79,7 @@ class _Scratch:
 
 class _RasterizeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pos, tri, H, W, nb, want_db=True, grad_db=False):
+    def forward(ctx, pos, tri, H, W, nb, want_db=True, grad_db=False, prev=None, ranges=None):
         lib = L.lib()
         pos_c = pos.contiguous().float()
         dev = pos.device
@@ -59,14 +89,24 @@ class _RasterizeFn(torch.autograd.Function):
         db = torch.empty((nb, H, W, 4) if want_db else (0,), dtype=torch.float32, device=dev)
         zbuf = _Scratch.get('zbuf', nb * H * W * 8, dev)
         big, big_cap = None, 0
-        if nf >= BIN_MIN_TRIS:
-            # tile-binned rasteriser (csrc/raster.hip: raster_tile_kernel): header + room for BIN_PAIRS_PER_TRI (triangle, tile) pairs per triangle
-            # and frame; a render that needs more falls back on the device to the wave-per-triangle kernels -- no host read-back
-            nt = nb * (-(-W // 32)) * (-(-H // 32))
-            big_cap = min(3 * nt + 8 + BIN_PAIRS_PER_TRI * nf * nb + nf, (1 << 31) - 1)
-            big = _Scratch.get('bins', 4 * big_cap, dev).view(torch.int32)
-        L.check(lib.d3h_rasterize_fwd(L.ptr(pos_c), L.i32(nv), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(nf), L.i32(nb), L.i32(H), L.i32(W),
-                                      L.ptr(zbuf), L.ptr(big), L.i32(big_cap), L.ptr(rast), L.ptr(db if want_db else None), L.stream()), 'rasterize_fwd')
+        if prev is not None or ranges is not None:
+            # a peeled layer (prev: the previous layer's rast) and / or range mode (ranges: (device [nb, 2] int32, largest count)): the
+            # wave-per-triangle path of d3h_rasterize_peel_fwd; the previous keys go to a scratch of their own, next to the shared z-buffer
+            pk = _Scratch.get('peel_keys', nb * H * W * 8, dev) if prev is not None else None
+            rg, max_count = ranges if ranges is not None else (None, 0)
+            L.check(lib.d3h_rasterize_peel_fwd(L.ptr(pos_c), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(nf), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rg),
+                                               L.i32(max_count), L.ptr(prev), L.ptr(pk), L.ptr(zbuf), L.ptr(rast), L.ptr(db if want_db else None),
+                                               L.stream()), 'rasterize_peel_fwd')
+        else:
+            if nf >= BIN_MIN_TRIS:
+                # tile-binned rasteriser (csrc/raster.hip: raster_tile_kernel): header + room for BIN_PAIRS_PER_TRI (triangle, tile) pairs per
+                # triangle and frame; a render that needs more falls back on the device to the wave-per-triangle kernels -- no host read-back
+                nt = nb * (-(-W // 32)) * (-(-H // 32))
+                big_cap = min(3 * nt + 8 + BIN_PAIRS_PER_TRI * nf * nb + nf, (1 << 31) - 1)
+                big = _Scratch.get('bins', 4 * big_cap, dev).view(torch.int32)
+            L.check(lib.d3h_rasterize_fwd(L.ptr(pos_c), L.i32(nv), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(nf), L.i32(nb), L.i32(H), L.i32(W),
+                                          L.ptr(zbuf), L.ptr(big), L.i32(big_cap), L.ptr(rast), L.ptr(db if want_db else None), L.stream()),
+                    'rasterize_fwd')
         ctx.save_for_backward(pos_c, tri, rast)
         ctx.dims = (H, W, nb)
         if not (grad_db and want_db):
@@ -87,20 +127,55 @@ class _RasterizeFn(torch.autograd.Function):
             L.check(L.lib().d3h_rasterize_bwd_db(L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rast),
                                                  L.ptr(g_rast.contiguous() if g_rast is not None else None), L.ptr(g_db.contiguous()),
                                                  L.ptr(d_pos), L.stream()), 'rasterize_bwd_db')
-            return d_pos, None, None, None, None, None, None
+            return (d_pos,) + (None,) * 8
         if g_rast is None:                     # nothing flowed into the barycentrics: the position gradient through them is zero
-            return d_pos, None, None, None, None, None, None
+            return (d_pos,) + (None,) * 8
         L.check(L.lib().d3h_rasterize_bwd(L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rast),
                                           L.ptr(g_rast.contiguous()), L.ptr(d_pos), L.stream()), 'rasterize_bwd')
-        return d_pos, None, None, None, None, None, None
+        return (d_pos,) + (None,) * 8
 
 
-def rasterize(pos, tri, resolution, nb=None, want_db=True, grad_db=False):
+def _check_ranges(ranges, nf):
+    """refuses anything but an int32 CPU tensor [B, 2] of (start, count) rows inside [0, nf]; -> the largest count (it sizes the grid)"""
+    if not (isinstance(ranges, torch.Tensor) and ranges.device.type == 'cpu' and ranges.dtype == torch.int32 and ranges.dim() == 2
+            and ranges.shape[1] == 2 and ranges.shape[0] > 0):
+        got = (ranges.dtype, ranges.device.type, tuple(ranges.shape)) if isinstance(ranges, torch.Tensor) else type(ranges).__name__
+        raise ValueError(f'rasterize: ranges must be an int32 CPU tensor [B, 2] with B >= 1, not {got}')
+    r = ranges.long()
+    if bool((r < 0).any()):
+        raise ValueError('rasterize: ranges holds a negative start or count')
+    if bool((r[:, 0] + r[:, 1] > nf).any()):
+        raise ValueError(f'rasterize: a range reaches past the {nf} triangles of tri')
+    return int(r[:, 1].max())
+
+
+def rasterize(pos, tri, resolution, nb=None, want_db=True, grad_db=False, prev_rast=None, ranges=None):
     """-> (rast [B,H,W,4] = (u, v, z/w, tri_id+1), rast_db [B,H,W,4] = (du/dX, du/dY, dv/dX, dv/dY); want_db False (extension): rast_db is None).
-    grad_db True: rast_db is differentiable in pos (module docstring); False: it is returned without a gradient."""
+    grad_db True: rast_db is differentiable in pos (module docstring); False: it is returned without a gradient.
+    prev_rast: the previous depth-peeling layer (a rast of these pos / tri / ranges) -> the next one.  ranges (with a 2-D pos [V,4]): range
+    mode, an int32 CPU tensor [B,2] of (start, count) into tri; ignored with a 3-D pos, as in nvdiffrast (module docstring)."""
     H, W = int(resolution[0]), int(resolution[1])
+    tri = tri.contiguous()
+    rg = None
+    if pos.dim() == 2:
+        if ranges is None:
+            raise ValueError('rasterize: a 2-D pos [V, 4] needs ranges (range mode); instanced mode takes pos [B, V, 4]')
+        if pos.shape[1] != 4:
+            raise ValueError(f'rasterize: pos must be [V, 4] in range mode, not {tuple(pos.shape)}')
+        max_count = _check_ranges(ranges, tri.shape[0])
+        nb = ranges.shape[0]
+        rg = ranges.contiguous()
+        if pos.is_cuda:                        # (a pageable copy would stall the host until the device drained its queue)
+            rg = rg.pin_memory().to(pos.device, non_blocking=True)
+        rg = (rg, max_count)
+        pos = pos[None]
     nb = pos.shape[0] if nb is None else nb
-    rast, db = _RasterizeFn.apply(pos, tri.contiguous(), H, W, nb, bool(want_db), bool(grad_db))
+    prev = None
+    if prev_rast is not None:
+        if tuple(prev_rast.shape) != (nb, H, W, 4) or prev_rast.dtype != torch.float32 or prev_rast.device != pos.device:
+            raise ValueError(f'rasterize: prev_rast must be a float32 [{nb}, {H}, {W}, 4] raster on {pos.device}')
+        prev = prev_rast.detach().contiguous()
+    rast, db = _RasterizeFn.apply(pos, tri, H, W, nb, bool(want_db), bool(grad_db), prev, rg)
     return rast, (db if want_db else None)
 
 
@@ -282,11 +357,16 @@ def aux_buffers(clip, rast, db, tri, gb_pos, view_pos, want_z=True, want_depth=T
     return z, dep, inv
 
 
-def _hash_for(tri):
-    nf = tri.shape[0]
+def _hash_cap(nf):
     cap = 1024
     while cap < 12 * max(nf, 1):
         cap *= 2
+    return cap
+
+
+def _hash_for(tri):
+    nf = tri.shape[0]
+    cap = _hash_cap(nf)
     dev = tri.device
     kv = _Scratch.get('aa_keys_vals', cap * 16, dev)          # keys [cap] uint64 | vals [2 cap] int32, contiguous: the library fills both at once
     keys, vals = kv[:cap * 8], kv[cap * 8:cap * 16]
@@ -294,10 +374,32 @@ def _hash_for(tri):
     return keys, vals, cap
 
 
-def _edge_flags(pos_c, tri, nb, H, W):
+class TopologyHash:
+    """antialias_construct_topology_hash(tri): the edge hash of d3h_antialias_hash built once, in buffers of its own (not the shared
+    scratch), for antialias(..., topology_hash=...) to reuse instead of rebuilding it on every call.  Valid for this triangle count
+    (antialias refuses another one) and meant for this very `tri`: the hash is a function of its contents."""
+
+    def __init__(self, tri):
+        tri = tri.contiguous()
+        nf = tri.shape[0]
+        cap = _hash_cap(nf)
+        kv = torch.empty(cap * 16, dtype=torch.uint8, device=tri.device)          # one allocation: keys | vals, as _hash_for's
+        self.keys, self.vals, self.cap, self.nf = kv[:cap * 8], kv[cap * 8:], cap, nf
+        L.check(L.lib().d3h_antialias_hash(L.ptr(tri), L.i32(nf), L.ptr(self.keys), L.ptr(self.vals), L.i32(cap), L.stream()), 'antialias_hash')
+
+
+def antialias_construct_topology_hash(tri):
+    """nvdiffrast.antialias_construct_topology_hash: -> a TopologyHash for antialias(..., topology_hash=...)"""
+    return TopologyHash(tri)
+
+
+def _edge_flags(pos_c, tri, nb, H, W, topology_hash=None):
     """[nb, nf] uint8: the silhouette-edge bits of every triangle in every frame (csrc/raster.hip:aa_edge_flags_kernel)"""
     nf = tri.shape[0]
-    keys, vals, cap = _hash_for(tri)
+    if topology_hash is None:
+        keys, vals, cap = _hash_for(tri)
+    else:
+        keys, vals, cap = topology_hash.keys, topology_hash.vals, topology_hash.cap
     flags = torch.empty(nb, max(nf, 1), dtype=torch.uint8, device=pos_c.device)
     L.check(L.lib().d3h_antialias_flags(L.ptr(pos_c), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(nf), L.i32(nb), L.ptr(keys), L.ptr(vals), L.i32(cap),
                                         L.i32(H), L.i32(W), L.ptr(flags), L.stream()), 'antialias_flags')
@@ -306,15 +408,16 @@ def _edge_flags(pos_c, tri, nb, H, W):
 
 class _AntialiasFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, color, rast, pos, tri):
+    def forward(ctx, color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0):
         lib = L.lib()
         color_c, rast_c, pos_c = color.contiguous().float(), rast.contiguous(), pos.contiguous().float()
         nb, H, W, C = color_c.shape
-        flags = _edge_flags(pos_c, tri, nb, H, W)        # per render; the backward reuses them (nb x nf bytes)
+        flags = _edge_flags(pos_c, tri, nb, H, W, topology_hash)        # per render; the backward reuses them (nb x nf bytes)
         out = torch.empty_like(color_c)
         L.check(lib.d3h_antialias_fwd(L.ptr(color_c), L.ptr(rast_c), L.ptr(pos_c), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(tri.shape[0]),
                                       L.ptr(flags), L.i32(nb), L.i32(H), L.i32(W), L.i32(C), L.ptr(out), L.stream()), 'antialias_fwd')
         ctx.save_for_backward(color_c, rast_c, pos_c, tri, flags)
+        ctx.boost = float(pos_gradient_boost)
         return out
 
     @staticmethod
@@ -326,11 +429,24 @@ class _AntialiasFn(torch.autograd.Function):
         L.check(L.lib().d3h_antialias_bwd(L.ptr(color), L.ptr(rast), L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(tri.shape[0]), L.ptr(flags),
                                           L.i32(nb), L.i32(H), L.i32(W), L.i32(C), L.ptr(g_out.contiguous()), L.ptr(g_color), L.ptr(d_pos),
                                           L.stream()), 'antialias_bwd')
-        return g_color, None, d_pos, None
+        if d_pos is not None and ctx.boost != 1.0:
+            d_pos.mul_(ctx.boost)
+        return g_color, None, d_pos, None, None, None
 
 
 def antialias(color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0):
-    return _AntialiasFn.apply(color, rast, pos, tri.contiguous())
+    """nvdiffrast.antialias.  pos [B or 1, V, 4], or [V, 4] (range mode: shared by every frame, d_pos summed over them); silhouettes come
+    from the topology of the whole tri.  topology_hash: antialias_construct_topology_hash(tri), reused instead of rebuilt (bit-identical
+    results).  pos_gradient_boost: d_pos is multiplied by it; the colour gradient is not."""
+    tri = tri.contiguous()
+    if topology_hash is not None:
+        if not isinstance(topology_hash, TopologyHash):
+            raise TypeError(f'antialias: topology_hash must come from antialias_construct_topology_hash, not {type(topology_hash).__name__}')
+        if topology_hash.nf != tri.shape[0]:
+            raise ValueError(f'antialias: topology_hash was built for {topology_hash.nf} triangles, tri has {tri.shape[0]}')
+    if pos.dim() == 2:
+        pos = pos[None]
+    return _AntialiasFn.apply(color, rast, pos, tri, topology_hash, float(pos_gradient_boost))
 
 
 class _TextureFn(torch.autograd.Function):

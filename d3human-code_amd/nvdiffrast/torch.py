@@ -1,7 +1,8 @@
 """Shim under the third-party name so `import nvdiffrast.torch as dr` (train.py:19, render/*.py) resolves to the
-MI355X kernels of csrc/raster.hip and csrc/texture.hip.  Only the entry points the reference calls are provided."""
+MI355X kernels of csrc/raster.hip and csrc/texture.hip: rasterize (instanced and range mode), DepthPeeler, interpolate, antialias,
+antialias_construct_topology_hash, texture, texture_construct_mip.  The OpenGL-only options of nvdiffrast are not provided."""
 from d3h import raster as _raster, texture as _texture
-from d3h.raster import antialias, interpolate, rasterize as _rasterize  # noqa: F401
+from d3h.raster import antialias, antialias_construct_topology_hash, interpolate, rasterize as _rasterize  # noqa: F401
 from d3h.texture import TextureMip, texture_construct_mip  # noqa: F401
 
 
@@ -15,29 +16,41 @@ RasterizeCudaContext = RasterizeGLContext
 
 
 def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
-    """nvdiffrast's defaults: with grad_db (the default) the pixel derivatives are differentiable in pos; without, they come back detached"""
-    return _rasterize(pos, tri, resolution, grad_db=grad_db)
+    """nvdiffrast's defaults: with grad_db (the default) the pixel derivatives are differentiable in pos; without, they come back detached.
+    ranges: range mode with a 2-D pos [V, 4] (d3h/raster.py's docstring), ignored with a 3-D pos"""
+    return _rasterize(pos, tri, resolution, grad_db=grad_db, ranges=ranges)
 
 
 class DepthPeeler:
-    """render/render.py:400-403 uses exactly one layer; the first layer is a plain rasterize (grad_db as in rasterize)"""
+    """nvdiffrast's depth peeling (d3h/raster.py's docstring states the contract).  The first layer is a plain rasterize -- the same entry
+    point and cost as before, the one layer render/render.py:400-403 uses; every later layer peels the previous one, whose `rast` this
+    object keeps: modifying it in place between two calls is refused rather than peeled from.  After the last non-empty layer the calls
+    return empty layers."""
     def __init__(self, glctx, pos, tri, resolution, ranges=None, grad_db=True):
         self.pos, self.tri, self.res = pos, tri, resolution
+        self.ranges = ranges
         self.grad_db = grad_db
         self.layer = 0
+        self.prev, self.prev_version = None, None
 
     def __enter__(self):
         return self
 
     def __exit__(self, *a):
+        self.prev = None
         return False
 
     def rasterize_next_layer(self, want_db=True):
         """want_db False (extension): the caller reads no pixel derivatives; the second result is None"""
         if self.layer > 0:
-            raise NotImplementedError('d3h DepthPeeler: only the first layer (the reference asserts num_layers == 1)')
+            if self.prev is None:
+                raise RuntimeError('DepthPeeler: rasterize_next_layer after the peeler was closed')
+            if self.prev._version != self.prev_version:
+                raise RuntimeError('DepthPeeler: the previous layer\'s rast was modified in place; depth peeling needs it as it was returned')
+        rast, db = _rasterize(self.pos, self.tri, self.res, want_db=want_db, grad_db=self.grad_db, prev_rast=self.prev, ranges=self.ranges)
+        self.prev, self.prev_version = rast, rast._version
         self.layer += 1
-        return _rasterize(self.pos, self.tri, self.res, want_db=want_db, grad_db=self.grad_db)
+        return rast, db
 
 
 def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='auto', boundary_mode='wrap', max_mip_level=None):
