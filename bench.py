@@ -24,16 +24,20 @@ bench contract); `optimizer_steps_per_s` (= K / T) and `frames_per_s` stand besi
   --as-rank-of W    ONE GPU, no process group: this process runs exactly the work of rank --rank-index (default W // 2) of a W-rank job
                     (d3h.dist_ops virtual-rank mode: the sdf shards of the other ranks come from a resident full sweep, learning rates at
                     zero so they stay exact; every kernel and every byte of glue of a real rank's step runs) and prints its step time.
-Without --frames-total the same invocation ALSO times configs[3] (8 frames in total over the N ranks) after the headline run and
-reports it as `config.config4_frames_total_8`; the N = 1 run additionally measures one virtual rank of W = 2, 4, 8 for both forms and
-emits `config.predicted_scaling` (rank time + the xGMI model of the collectives).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line, and nothing else.  Whatever else the
+benchmark measures runs after the timed steps with --full only (--no-extras, --no-predict and --no-cpu-baseline leave parts of it out):
+without --frames-total configs[3] (8 frames in total over the N ranks) as `config.config4_frames_total_8`; the 12-buffer and exact-f32
+rates; a second pass of the step with HIP events around the image-space / mesh kernels; the RCCL floors of the step's collectives; for
+N > 1 the other mode of the frame-independent work (--both-modes asks for it alone); for N = 1 one virtual rank of W = 2, 4, 8 for both
+forms as `config.predicted_scaling` (rank time + the xGMI model of the collectives) and `cpu_baseline`; for --config 5 the LPIPS trunk.
 
 Prints ONE JSON line < 4 KB as the last line of stdout (rank 0; short_line()): the contract's keys, `config` (workload, frames, faces,
-the 12-buffer and exact-f32 rates, for N > 1 world size / backend / collective microseconds), the `roofline` of the dominant kernel (the
-fused SDF query on the matrix pipe; HIP events on its launch stream inside the timed region, csrc/timing.hip) and `cpu_baseline` (the
-oracle tick of configs[1] on the host cores + the parity of that very run as scalars).  The FULL record -- `rooflines` of the other
-heavy kernels, `predicted_scaling`, the whole parity report, per-stage CPU seconds -- is written to bench_detail.json beside this script
-($D3H_BENCH_DETAIL overrides; emit()), never to stdout: the round-4 line had grown to 23 KB and the driver could not parse it.
+for N > 1 world size / backend / collective microseconds; with --full the 12-buffer and exact-f32 rates), the `roofline` of the dominant
+kernel (the fused SDF query on the matrix pipe; HIP events on its launch stream inside the timed region, csrc/timing.hip) and, with
+--full, `cpu_baseline` (the oracle tick of configs[1] on the host cores + the parity of that very run as scalars).  The FULL record --
+`rooflines` of the other heavy kernels, `predicted_scaling`, the whole parity report, per-stage CPU seconds -- is written to
+bench_detail.json beside this script ($D3H_BENCH_DETAIL overrides; emit()), never to stdout: the round-4 line had grown to 23 KB and the
+driver could not parse it.
 
 --dump-outputs DIR: after the timed steps, the losses of the last one, the parameters after it and their gradients as DIR/<name>.npy
 (step_outputs(), dump_outputs()).  The steps of the headline scene run at learning rate zero (every kernel of the step still runs, Adam
@@ -524,19 +528,27 @@ def main():
                                                   "f3c = the reference's own working point (configs/f3c.json: batch 1, 1080x1080, tet grid 128, init-stage loss stack with the MobileNetV2 normal loss)")
     ap.add_argument('--frames-total', type=int, default=0, help='strong scaling (BASELINE configs[3]): this many frames in total, split over the ranks')
     ap.add_argument('--shard-sweep', action='store_true', help='(accepted for compatibility: sharding the frame-independent work is the default for N > 1)')
-    ap.add_argument('--both-modes', action='store_true', help='N > 1: measure the other mode (sharded <-> replicated) too, even with --no-extras (the default full run does)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline run, everything else the benchmark measures: the 12-buffer and exact-f32 rates, configs[3] (8 frames), '
+                         'the other mode of N > 1, the RCCL floors, the predicted 2/4/8-GPU table, the launch times of the image-space kernels, the '
+                         'LPIPS trunk (--config 5) and the CPU baseline with its parity report.  Without it a run sets up, warms up, times the '
+                         'steps, writes --dump-outputs and prints the result line')
+    ap.add_argument('--both-modes', action='store_true', help='N > 1: measure the other mode (sharded <-> replicated) too, even without --full or with --no-extras')
     ap.add_argument('--replicate', action='store_true', help='N > 1: replicate the SDF sweep and all eikonal samples on every rank (one collective per step)')
     ap.add_argument('--as-rank-of', type=int, default=0, help='one GPU stands in for one rank of a W-rank job (virtual-rank mode); prints that rank\'s step time')
     ap.add_argument('--rank-index', type=int, default=-1, help='which rank --as-rank-of plays (default W // 2: the slice of the grid with the most surface)')
-    ap.add_argument('--no-predict', action='store_true', help='skip the predicted 2/4/8-GPU table of the N = 1 run')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the 12-buffer rate')
+    ap.add_argument('--no-predict', action='store_true', help='--full: skip the predicted 2/4/8-GPU table of the N = 1 run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the other rates (12 buffers, exact f32, configs[3], other mode, RCCL floors, '
+                                                            'predicted table)')
     ap.add_argument('--all-buffers', action='store_true', help='time the step with all 12 reference buffers composited + antialiased (render.py:430-449) instead of the loss-consumed three')
     ap.add_argument('--prefit', type=int, default=300)
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last of them computed (losses, updated parameters, their gradients) as DIR/<name>.npy')
     args = ap.parse_args()
     args.config = int(args.config) if str(args.config).isdigit() else str(args.config)
+    full_extras = args.full and not args.no_extras             # nothing beside the headline figure runs without --full
+    cpu_base = args.full and not args.no_cpu_baseline
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
@@ -715,7 +727,8 @@ def main():
     recs = collect_kernel_timing(lib) if rank == 0 else []
     coll = sc.coll_timing
     sc.coll_timing = None
-    if os.environ.get('D3H_BENCH_NO_KTIME') != '1':
+    second_pass = args.full and os.environ.get('D3H_BENCH_NO_KTIME') != '1'
+    if second_pass:
         lib.d3h_timing_select(ctypes.c_uint64(~SDF_KT_MASK & 0xFFFFFFFFFFFFFFFF))
         lib.d3h_timing_enable(1)
         for _ in range(min(20, args.steps)):          # every rank runs them: the step contains the gradient all-reduce
@@ -738,7 +751,7 @@ def main():
     if 'buffers' in sc.geometry.last_mesh_dict:
         cov_px = float((sc.geometry.last_mesh_dict['buffers']['shaded'][..., 3] > 0).sum())
     dt12 = None
-    if not args.no_extras and not args.all_buffers and cfg['loss_set'] == 'full':
+    if full_extras and not args.all_buffers and cfg['loss_set'] == 'full':
         save = sc.FLAGS.render_buffers
         sc.FLAGS.render_buffers = 'all'                   # all 12 buffers composited + antialiased, as the reference does every iteration
         for _ in range(3):
@@ -755,7 +768,7 @@ def main():
     # ---- the same step with the exact-f32 MFMA kernels (D3H_SDF_X3=0), same process, same scene: what the bf16 x 3 arithmetic buys --------
     dt_f32 = None
     from d3h import sdf_mlp as _smx
-    if not args.no_extras and world == 1 and getattr(_smx, 'X3', False):
+    if full_extras and world == 1 and getattr(_smx, 'X3', False):
         _smx.X3 = False
         try:
             dt_f32 = timed_steps(step, max(5, args.steps // 4)) * 1e-3
@@ -766,7 +779,7 @@ def main():
         sync()
     # ---- the GPU rate of BASELINE configs[1] (the configuration the CPU baseline is timed on), single-GPU run only ----------------------
     gpu_cfg2 = sc2 = None
-    if not args.no_cpu_baseline and world == 1 and args.config == 3:
+    if cpu_base and world == 1 and args.config == 3:
         sc2 = scene.Scene(device=dev, prefit_steps=args.prefit, visualize_watertight=True, res=512, grid_n=32, n_frames=1, loss_set='mask')
         for _ in range(10):
             sc2.step()
@@ -779,7 +792,7 @@ def main():
         gpu_cfg2 = 60 / (time.time() - t1)
     # ---- BASELINE configs[3] in the same invocation: 8 frames in total over the ranks (8 / N per GPU), "strong" -------------------------
     cfg4 = None
-    if not args.no_extras and not strong and not args.all_buffers and cfg['loss_set'] == 'full' and 8 % world == 0:
+    if full_extras and not strong and not args.all_buffers and cfg['loss_set'] == 'full' and 8 % world == 0:
         f4 = 8 // world
         sc4 = scene.Scene(device=dev, prefit_steps=args.prefit, visualize_watertight=True, dist_world=world, dist_rank=rank,
                           frame_seed=1234 + rank * f4, flags_hook=lambda F: setattr(F, 'eikonal_samples', EIK_TOTAL),
@@ -819,7 +832,7 @@ def main():
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)
         ranks_seen = int(ones.item())
-    if world > 1 and ((not args.no_extras and cfg['loss_set'] == 'full') or args.both_modes):
+    if world > 1 and ((full_extras and cfg['loss_set'] == 'full') or args.both_modes):
         (sc.disable_work_sharding if shard else sc.enable_work_sharding)(EIK_TOTAL)
         for _ in range(3):
             step()
@@ -839,7 +852,7 @@ def main():
     # ---- the per-call floor of the step's three collectives at their real sizes, on RCCL: the real group for N > 1, a ONE-rank group on a
     # single-GPU run (launch + kernel floor, no wire) -- replaces the assumed 30 us in the model of predicted_scaling ----
     rccl_floor = None
-    if not args.no_extras and cfg['loss_set'] in ('full', 'init', 'mask'):
+    if full_extras and cfg['loss_set'] in ('full', 'init', 'mask'):
         from d3h import dist_ops as _D
         made = False
         try:
@@ -861,7 +874,7 @@ def main():
     # ---- predicted 2 / 4 / 8-GPU table: one virtual rank of each world size, measured here, + the xGMI model of the collectives ----------
     last_loss = {k: float(v) for k, v in sc.last.items()}
     predicted = None
-    if world == 1 and not args.no_extras and not args.no_predict and not strong and not args.all_buffers and cfg['loss_set'] == 'full' and cfg4 is not None:
+    if world == 1 and full_extras and not args.no_predict and not strong and not args.all_buffers and cfg['loss_set'] == 'full' and cfg4 is not None:
         scs = {cfg['n_frames']: sc}
         for f_ in (2, 1):
             scs[f_] = scene.Scene(device=dev, prefit_steps=args.prefit, visualize_watertight=True, frame_seed=1234,
@@ -996,11 +1009,12 @@ def main():
                           sorted(1e3 * (b - a) for a, b in zip(marks[:-1], marks[1:])))},
            'roofline': roof, 'rooflines': rooflines,
            'rooflines_note': ('HIP events on the launch streams: the SDF-network kernels (the first entries, incl. `roofline`) inside the timed '
-                              'region, the image-space / mesh kernels in a second pass of %d steps right after it (their ~45 event pairs per '
-                              'step cost 0.12 ms of host time on the launch path)' % min(20, args.steps))}
+                              'region, ' + ('the image-space / mesh kernels in a second pass of %d steps right after it' % min(20, args.steps)
+                                            if second_pass else 'the image-space / mesh kernels only with --full, in a second pass') +
+                              ' (their ~45 event pairs per step cost 0.12 ms of host time on the launch path)')}
     if getattr(sc, 'split_faces', None):
         out['config']['split_faces'] = sc.split_faces
-    if lp is not None:
+    if lp is not None and args.full:
         # the LPIPS trunk (AlexNet features through MIOpen) as a roofline entry of its own: the prediction side of one tick_split call, forward +
         # input gradient, timed in isolation with HIP events; x 2 calls per iteration.  FLOPs: the five convolutions at this resolution (2 x MACs)
         r_ = cfg['res']
@@ -1058,7 +1072,7 @@ def main():
         out['value_note'] = ('value = N x K / T counts rank-iterations (the bench contract: units all ranks processed / time); one OPTIMISER step of '
                              'the job consumes N x %d frames and takes T / K: optimizer_steps_per_s and frames_per_s are the training-speed figures'
                              % cfg['n_frames'])
-    if not args.no_cpu_baseline and world == 1:          # the CPU baseline is measured once, on the single-GPU run
+    if cpu_base and world == 1:          # the CPU baseline is measured once, on the single-GPU run
         # measured: BASELINE configs[1] through the whole oracle tick; beside it the GPU rate of the SAME config, and -- as a second, stated
         # ESTIMATE -- the config-3 figure assembled from per-stage timings scaled by each stage's size law
         # the state the oracle tick is timed (and compared) on: the REPRODUCIBLE one of tests/test_gpu_fullsize.py -- the CPU-fitted SDF network

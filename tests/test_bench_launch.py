@@ -1,7 +1,8 @@
 """bench.py --gpus N starts its own ranks (north star: one process per GPU over RCCL; the reference has no launcher, train.py:1645-1655).
 CPU: the launcher's failure semantics -- a rank that dies gives a non-zero exit and NO result line, a mislabelled launch is refused.
 -m gpu: `python bench.py --gpus 2` end to end on a one-GPU box over the gloo / shared-device loopback (RCCL refuses two ranks on one
-device; everything else of the N > 1 path runs: rendezvous, parameter broadcast, the gradient bucket, barriers, max-over-ranks timing)."""
+device; everything else of the N > 1 path runs: rendezvous, parameter broadcast, the gradient bucket, barriers, max-over-ranks timing), and
+a plain one-GPU run that does only what its headline figure needs (everything else waits for --full)."""
 import json
 import os
 import subprocess
@@ -56,3 +57,22 @@ def test_gpu_bench_gpus_2_self_launch_loopback(gpu):
     assert d['config']['rccl_ranks_seen'] == 2 and d['config']['mode'] == 'shard'
     om = d['config']['other_mode']
     assert om['mode'] == 'replicate' and om['value'] > 0 and om['collectives_per_step'] == 1
+
+
+@pytest.mark.gpu
+def test_gpu_plain_run_times_the_steps_and_nothing_else(gpu, tmp_path):
+    """without --full: set-up, warm-up, the timed steps, --dump-outputs and the result line; none of the other rates, the CPU baseline, the RCCL
+    floors or the second kernel-timing pass"""
+    detail = tmp_path / 'detail.json'
+    r = _run(['--steps', '3', '--warmup', '1', '--config', '2', '--prefit', '50', '--dump-outputs', str(tmp_path / 'dump')],
+             env={'D3H_BENCH_DETAIL': str(detail)})
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.splitlines()[-1])
+    assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['value'] > 0 and d['roofline'] is not None
+    assert 'cpu_baseline' not in d
+    full = json.load(open(detail))
+    for k in ('all_12_buffers_iters_per_s', 'exact_f32_mfma_iters_per_s', 'config4_frames_total_8', 'predicted_scaling', 'rccl_floor_us'):
+        assert k not in full['config'], k
+    assert full['rooflines'] and all(e['kernel'].startswith('sdf_mlp') for e in full['rooflines'])
+    dumped = os.listdir(tmp_path / 'dump')
+    assert 'loss.total.npy' in dumped and any(f.startswith('grad.') for f in dumped)

@@ -13,7 +13,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 # (the stdout line is the short result line the driver parses; the full record -- rooflines, predicted_scaling, parity -- is the detail file)
-cd $REPO && D3H_BENCH_DETAIL=$OUT/${TAG}_bench_config3_detail.json python3 bench.py --steps 100 --warmup 10 > $OUT/${TAG}_bench_config3.json 2> $OUT/bench.err
+cd $REPO && D3H_BENCH_DETAIL=$OUT/${TAG}_bench_config3_detail.json python3 bench.py --steps 100 --warmup 10 --full > $OUT/${TAG}_bench_config3.json 2> $OUT/bench.err
 bash tools/profile_bench.sh $TAG --no-extras
 for k in kernel_stats per_iteration per_iteration_serialised timeline; do cp gpurun_out/prof_${TAG}_$k.csv $OUT/${TAG}_bench_config3_$k.csv; done
 cd /tmp && export TMPDIR=/tmp
