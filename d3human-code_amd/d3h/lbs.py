@@ -3,6 +3,11 @@
 Mirrors deform/smplx_exavatar_deformer.py: interpolate_weights :363-383 (K=1), apply_lbs_inverse :385-421,
 lbs_forward :434-486 -- for a whole batch of frames at once (the nearest-vertex ids depend only on the canonical
 points, so they are computed once and shared by every frame).
+
+K > 1 (the reference's `self.k`, :40,:366): knnk / KnnGrid.query_k search the K nearest template vertices (1 <= K <= 32, ascending in
+(squared distance, index): among equal distances the lower index first) and lbs_points_k skins with the inverse-distance blend of their
+weight rows (:367-381); its backward carries the gradient through the blend weights to the point.  K = 1 keeps its own entry points
+(knn1, lbs_points) and kernels.
 """
 import ctypes
 
@@ -71,6 +76,101 @@ class KnnGrid:
                                   self.lo, L.f32(self.h), L.i32(self.g[0]), L.i32(self.g[1]), L.i32(self.g[2]), L.ptr(idx),
                                   L.ptr(dist), L.stream()), 'knn1_grid')
         return (idx, dist) if want_dist else idx
+
+    def query_k(self, pts, K):
+        """the K nearest template vertices of every point -> KnnResult(idx [P,K] int32, d2 [P,K]); exactly what knnk returns without a grid"""
+        pts = _knnk_args(pts, K)
+        P = pts.shape[0]
+        idx = torch.empty(P, K, dtype=torch.int32, device=pts.device)
+        d2 = torch.empty(P, K, dtype=torch.float32, device=pts.device)
+        L.check(L.lib().d3h_knnk_grid(L.ptr(pts), L.i32(P), L.ptr(self.cell_pts), L.ptr(self.cell_start), L.i32(self.nv), self.lo, L.f32(self.h),
+                                      L.i32(self.g[0]), L.i32(self.g[1]), L.i32(self.g[2]), L.i32(K), L.ptr(idx), L.ptr(d2), L.stream()), 'knnk_grid')
+        return KnnResult(idx, d2)
+
+    def query_k_counted(self, pts_cap, counts, K, out=None):
+        """query_k over the first counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` (a buffer at its capacity), the row count read on the
+        DEVICE -> KnnResult at the capacity; the other rows are not written (`out`: a KnnResult to write into)"""
+        pts = _knnk_args(pts_cap, K, convert=False)
+        cap = pts.shape[0]
+        if counts.dtype != torch.int32 or counts.numel() < 11 or not counts.is_contiguous():
+            raise RuntimeError('d3h query_k_counted: counts must be the contiguous int32 counter block of the extraction')
+        if out is None:
+            out = KnnResult(torch.empty(cap, K, dtype=torch.int32, device=pts.device), torch.empty(cap, K, dtype=torch.float32, device=pts.device))
+        _check_knn_result(out, cap, K, 'query_k_counted')
+        L.check(L.lib().d3h_knnk_grid_counted(L.ptr(pts), L.i32(cap), L.ptr(counts), L.ptr(self.cell_pts), L.ptr(self.cell_start), L.i32(self.nv),
+                                              self.lo, L.f32(self.h), L.i32(self.g[0]), L.i32(self.g[1]), L.i32(self.g[2]), L.i32(K), L.ptr(out.idx),
+                                              L.ptr(out.d2), L.stream()), 'knnk_grid_counted')
+        return out
+
+
+K_MAX = 32        # KNNK_MAX of csrc/lbs.hip
+
+
+class KnnResult:
+    """K nearest template vertices of P points: idx [P,K] int32, d2 [P,K] float32 squared distances.  Unpacks as `idx, d2 = r`; a slice
+    narrows the ROWS (`r[:p]`: the deformer's callers hand a search result on without looking into it)"""
+    __slots__ = ('idx', 'd2')
+
+    def __init__(self, idx, d2):
+        self.idx, self.d2 = idx, d2
+
+    def __iter__(self):
+        return iter((self.idx, self.d2))
+
+    def __len__(self):
+        return self.idx.shape[0]
+
+    def __getitem__(self, s):
+        if isinstance(s, slice):
+            return KnnResult(self.idx[s], self.d2[s])
+        return (self.idx, self.d2)[s]
+
+    @property
+    def K(self):
+        return self.idx.shape[1]
+
+
+def _check_K(K):
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= K_MAX:
+        raise ValueError(f'd3h knn: K must be an int in 1..{K_MAX}, got {K!r}')
+
+
+def _knnk_args(pts, K, convert=True):
+    _check_K(K)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise RuntimeError(f'd3h knn: points must be [P,3], got {tuple(pts.shape)}')
+    pts = pts.detach()
+    if convert:
+        return pts.contiguous().float()
+    if pts.dtype != torch.float32 or not pts.is_contiguous():
+        raise RuntimeError('d3h knn: the capacity buffer must be contiguous float32')
+    return pts
+
+
+def _check_knn_result(nn, P, K, what):
+    idx, d2 = nn.idx, nn.d2
+    if tuple(idx.shape) != (P, K) or tuple(d2.shape) != (P, K) or idx.dtype != torch.int32 or d2.dtype != torch.float32 or \
+            not idx.is_contiguous() or not d2.is_contiguous():
+        raise RuntimeError(f'd3h {what}: the search result must be contiguous idx int32 / d2 float32 of shape {(P, K)}, got '
+                           f'{tuple(idx.shape)} {idx.dtype} / {tuple(d2.shape)} {d2.dtype}')
+
+
+def knnk(pts, tmpl, K, grid=None):
+    """the K nearest template vertices of every point, 1 <= K <= 32 -> KnnResult(idx [P,K] int32, d2 [P,K] squared L2), ascending in
+    (distance, index): among equal distances the lower index stays and comes first (knn_cpu.cpp:39-66).  Slots tmpl.shape[0]..K-1 of a
+    template with fewer than K vertices hold index 0 and distance 0; a query without a finite distance holds index 0 and distance +inf.
+    `grid`: a KnnGrid of `tmpl` (same result)"""
+    if grid is not None:
+        return grid.query_k(pts, K)
+    pts = _knnk_args(pts, K)
+    if tmpl.dim() != 2 or tmpl.shape[1] != 3 or tmpl.shape[0] == 0:
+        raise RuntimeError(f'd3h knnk: the template must be [V,3] with V >= 1, got {tuple(tmpl.shape)}')
+    tmpl = tmpl.detach().contiguous().float()
+    P = pts.shape[0]
+    idx = torch.empty(P, K, dtype=torch.int32, device=pts.device)
+    d2 = torch.empty(P, K, dtype=torch.float32, device=pts.device)
+    L.check(L.lib().d3h_knnk(L.ptr(pts), L.i32(P), L.ptr(tmpl), L.i32(tmpl.shape[0]), L.i32(K), L.ptr(idx), L.ptr(d2), L.stream()), 'knnk')
+    return KnnResult(idx, d2)
 
 
 def knn1(pts, tmpl, grid=None):
@@ -143,6 +243,87 @@ def lbs_points_counted(pts_cap, counts, idx_cap, lbs_w, A0, A, trans):
     out = torch.empty(nb * cap * 3, dtype=torch.float32, device=pts_cap.device)
     L.check(lib.d3h_lbs_fwd_counted(L.ptr(pts_cap.detach()), L.i32(cap), L.ptr(counts), L.ptr(idx_cap), L.ptr(lbs_w.contiguous().float()), L.i32(nj),
                                     L.ptr(A0c), L.ptr(Ac), L.ptr(tr), L.i32(nb), L.ptr(out), L.stream()), 'lbs_fwd_counted')
+    return out
+
+
+def _lbsk_args(nn, lbs_w, tmpl, A0, A, trans, P, what):
+    K = nn.idx.shape[1] if nn.idx.dim() == 2 else 0
+    _check_K(K)
+    _check_knn_result(nn, P, K, what)
+    if lbs_w.dim() != 2 or tmpl.dim() != 2 or tmpl.shape[1] != 3 or tmpl.shape[0] != lbs_w.shape[0]:
+        raise RuntimeError(f'd3h {what}: lbs_w [V,J] and tmpl [V,3] expected, got {tuple(lbs_w.shape)} and {tuple(tmpl.shape)}')
+    A0c = A0.detach().reshape(-1, 16).contiguous().float()
+    Ac = A.detach().reshape(A.shape[0], -1, 16).contiguous().float()
+    tr = trans.detach().reshape(-1, 3).contiguous().float()
+    if A0c.shape[0] != lbs_w.shape[1] or Ac.shape[1] != lbs_w.shape[1] or tr.shape[0] != Ac.shape[0]:
+        raise RuntimeError(f'd3h {what}: {lbs_w.shape[1]} joints in lbs_w, A0 {tuple(A0.shape)}, A {tuple(A.shape)}, trans {tuple(trans.shape)}')
+    return K, A0c, Ac, tr
+
+
+class _LBSKFn(torch.autograd.Function):
+    """K-blended skinning: _LBSFn with the weight rows of the K nearest vertices blended by inverse distance; d(pts) includes the path
+    through the blend weights (the squared distances are functions of pts; the template is a constant)"""
+
+    @staticmethod
+    def forward(ctx, pts, idx, d2, lbs_w, tmpl, A0, A, trans, pre):
+        lib = L.lib()
+        pts_c = pts.contiguous().float()
+        P = pts_c.shape[0]
+        K, A0c, Ac, tr = _lbsk_args(KnnResult(idx, d2), lbs_w, tmpl, A0, A, trans, P, 'lbs_points_k')
+        nb, nj = Ac.shape[0], Ac.shape[1]
+        if pre is not None:                 # computed by lbs_points_k_counted from the same arguments before the row count was known on the host
+            if tuple(pre.shape) != (nb, P, 3) or not pre.is_contiguous():
+                raise RuntimeError(f'd3h lbs_points_k: the pre-computed result is {tuple(pre.shape)}, expected {(nb, P, 3)}')
+            out = pre
+        else:
+            out = torch.empty(nb, P, 3, dtype=torch.float32, device=pts.device)
+            L.check(lib.d3h_lbsk_fwd(L.ptr(pts_c), L.i32(P), L.ptr(idx), L.ptr(d2), L.i32(K), L.ptr(lbs_w), L.i32(nj), L.ptr(A0c), L.ptr(Ac),
+                                     L.ptr(tr), L.i32(nb), L.ptr(out), None, L.stream()), 'lbsk_fwd')
+        ctx.save_for_backward(pts_c, idx, d2, lbs_w, tmpl, A0c, Ac)
+        ctx.shapes = (A.shape, trans.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pts, idx, d2, lbs_w, tmpl, A0c, Ac = ctx.saved_tensors
+        lib = L.lib()
+        nb, nj, P, K = Ac.shape[0], Ac.shape[1], pts.shape[0], idx.shape[1]
+        g = g.contiguous().float()
+        need_p, need_A, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        d_pts = torch.empty_like(pts) if need_p else None
+        per_frame = torch.empty(nb, P, 3, dtype=torch.float32, device=pts.device) if need_p and nb > 1 else None   # summed in frame order
+        dA = L.zeros((nb, nj, 16), torch.float32, pts.device) if need_A else None
+        dT = L.zeros((nb, 3), torch.float32, pts.device) if need_t else None
+        L.check(lib.d3h_lbsk_bwd(L.ptr(pts), L.i32(P), L.ptr(idx), L.ptr(d2), L.i32(K), L.ptr(tmpl), L.ptr(lbs_w), L.i32(nj), L.ptr(A0c),
+                                 L.ptr(Ac), L.i32(nb), L.ptr(g), L.ptr(d_pts), L.ptr(per_frame), L.ptr(dA), L.ptr(dT), L.stream()), 'lbsk_bwd')
+        a_shape, t_shape = ctx.shapes
+        return (d_pts, None, None, None, None, None, dA.reshape(a_shape) if need_A else None, dT.reshape(t_shape) if need_t else None, None)
+
+
+def lbs_points_k(pts, nn, lbs_w, tmpl, A0, A, trans, pre=None):
+    """lbs_points with the skin weights blended over the K nearest template vertices: nn = KnnResult(idx [P,K], d2 [P,K]) of knnk(pts, tmpl, K),
+    a_k = u_k / sum u with u_k = 1 / (sqrt(d2_k + 1e-9) + 1e-9), w = sum_k a_k lbs_w[idx_k] (interpolate_weights :367-381)  ->  posed points
+    [B,P,3].  tmpl [V,3]: the template nn was searched in, a constant; the gradient of pts includes the one through the blend weights.
+    `pre`: the result already computed by lbs_points_k_counted"""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise RuntimeError(f'd3h lbs_points_k: points must be [P,3], got {tuple(pts.shape)}')
+    return _LBSKFn.apply(pts, nn.idx, nn.d2, lbs_w.detach().contiguous().float(), tmpl.detach().contiguous().float(), A0, A, trans, pre)
+
+
+def lbs_points_k_counted(pts_cap, counts, nn_cap, lbs_w, tmpl, A0, A, trans):
+    """lbs_points_k over the first r = counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` [capacity, 3] (nn_cap: query_k_counted of the same
+    buffer), r read on the DEVICE.  -> a flat float buffer whose leading B * r * 3 floats are the dense [B, r, 3] result (counted_result)"""
+    lib = L.lib()
+    pts = pts_cap.detach()
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous():
+        raise RuntimeError('d3h lbs_points_k_counted: the capacity buffer must be contiguous float32 [capacity,3]')
+    cap = pts.shape[0]
+    K, A0c, Ac, tr = _lbsk_args(nn_cap, lbs_w, tmpl, A0, A, trans, cap, 'lbs_points_k_counted')
+    nb, nj = Ac.shape[0], Ac.shape[1]
+    out = torch.empty(nb * cap * 3, dtype=torch.float32, device=pts.device)
+    L.check(lib.d3h_lbsk_fwd_counted(L.ptr(pts), L.i32(cap), L.ptr(counts), L.ptr(nn_cap.idx), L.ptr(nn_cap.d2), L.i32(K),
+                                     L.ptr(lbs_w.detach().contiguous().float()), L.i32(nj), L.ptr(A0c), L.ptr(Ac), L.ptr(tr), L.i32(nb), L.ptr(out),
+                                     L.stream()), 'lbsk_fwd_counted')
     return out
 
 

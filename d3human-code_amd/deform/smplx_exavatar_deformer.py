@@ -1,7 +1,11 @@
 """SMPL-X driven deformer with the reference's interface (deform/smplx_exavatar_deformer.py: SMPLX_Deformer :21,
 initialize :173, interpolate_weights :363, apply_lbs_inverse :385, lbs_forward :434), running on the HIP kernels of
 csrc/lbs.hip through d3h.lbs.  `lbs_forward_batch` is the build's N-frame extension (the reference poses
-every frame of a batch with idx[0])."""
+every frame of a batch with idx[0]).
+
+`k` (the reference's `self.k`, :40): the number of nearest template vertices whose skin-weight rows are blended by inverse distance
+(:366-381), 1..32.  It is a plain attribute read at call time (`deformer.k = 4` works as in the reference); k = 1 is the reference's
+setting and takes the single-neighbour kernels."""
 import numpy as np
 import torch
 from d3h.devconst import const as _const
@@ -23,11 +27,11 @@ def write_pc(path_mesh, v, vn=None, f=None):
 
 class SMPLX_Deformer(object):
     def __init__(self, model_path='smplx', gender='neutral', model_dict=None, device='cuda', shape_param_dim=100,
-                 expr_param_dim=50):
+                 expr_param_dim=50, k=1):
         self.shape_param_dim = shape_param_dim
         self.expr_param_dim = expr_param_dim
         self.model_path = model_path
-        self.k = 1
+        self.k = k
         self.device = device
         self.layer = SMPLX(model_path=model_path, gender=gender, num_betas=shape_param_dim,
                            num_expression_coeffs=expr_param_dim, model_dict=model_dict).to(device)
@@ -66,11 +70,29 @@ class SMPLX_Deformer(object):
         grid = getattr(self, '_knn_grid', None)
         if grid is None or not grid.matches(tmpl):
             grid = self._knn_grid = HL.KnnGrid(tmpl)
+        k = self._k()
+        if k > 1:                # the K nearest: HL.KnnResult(idx [P,K], d2 [P,K]), handed on to lbs_forward_batch(nn_idx=) as it is
+            return HL.knnk(pts.reshape(-1, 3), tmpl, k, grid=grid)
         return HL.knn1(pts.reshape(-1, 3), tmpl, grid=grid)
 
+    def _k(self):
+        k = self.k
+        if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= HL.K_MAX:
+            raise ValueError(f'SMPLX_Deformer.k must be an int in 1..{HL.K_MAX}, got {k!r}')
+        return k
+
     def interpolate_weights(self, pts):
-        """[B,P,3] -> [B,P,J]; with K=1 the inverse-distance weight is exactly 1 (:367-370)"""
+        """[B,P,3] -> [B,P,J]; with K=1 the inverse-distance weight is exactly 1 (:367-370).  K > 1: the inverse-distance blend of the K
+        nearest rows (:367-381), differentiable in pts (neighbours from the HIP search, the few blend operations in torch: this is the
+        reference-interface accessor, the skinning itself blends inside its kernels)"""
         B, P, _ = pts.shape
+        if self._k() > 1:
+            tmpl = self.vs_template[0]
+            idx = torch.stack([self.nearest(pts[b]).idx for b in range(B)]).long()                # [B,P,K]
+            dist = torch.sqrt(((pts[:, :, None, :] - tmpl[idx]) ** 2).sum(-1) + 1e-9)
+            w = 1.0 / (dist + 1e-9)
+            w = w / w.sum(dim=2, keepdim=True)
+            return (self.lbs_weights[idx] * w[..., None]).sum(dim=2)
         idx = torch.stack([self.nearest(pts[b]) for b in range(B)]).long()
         return self.lbs_weights[idx]
 
@@ -117,6 +139,8 @@ class SMPLX_Deformer(object):
         if nn_idx is None:
             nn_idx = self.nearest(pts)
         A, trans = transforms if transforms is not None else self.frame_transforms(smplx_param, idx_list)
+        if isinstance(nn_idx, HL.KnnResult):
+            return HL.lbs_points_k(pts, nn_idx, self.lbs_weights, self.vs_template[0], self.init_A[0], A, trans, pre=pre)
         return HL.lbs_points(pts, nn_idx, self.lbs_weights, self.init_A[0], A, trans, pre=pre)
 
     def nearest_counted(self, pts_cap, counts):
@@ -125,10 +149,15 @@ class SMPLX_Deformer(object):
         grid = getattr(self, '_knn_grid', None)
         if grid is None or not grid.matches(tmpl):
             grid = self._knn_grid = HL.KnnGrid(tmpl)
+        k = self._k()
+        if k > 1:
+            return grid.query_k_counted(pts_cap, counts, k)
         return grid.query_counted(pts_cap, counts)
 
     def lbs_forward_counted(self, pts_cap, counts, nn_idx_cap, transforms):
         A, trans = transforms
+        if isinstance(nn_idx_cap, HL.KnnResult):
+            return HL.lbs_points_k_counted(pts_cap, counts, nn_idx_cap, self.lbs_weights, self.vs_template[0], self.init_A[0], A, trans)
         return HL.lbs_points_counted(pts_cap, counts, nn_idx_cap, self.lbs_weights, self.init_A[0], A, trans)
 
     def lbs_forward(self, pts, smplx_param, idx, face=None):
