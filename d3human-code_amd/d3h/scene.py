@@ -73,7 +73,7 @@ class _ZeroOffset(torch.nn.Module):
 class Scene:
     def __init__(self, res=512, grid_n=32, n_frames=1, device='cuda', seed=0, prefit_steps=300, loss_set='full', body_verts=10475,
                  visualize_watertight=False, dist_world=1, dist_rank=0, sdf_fn=None, flags_hook=None, frame_seed=1234, lpips=None,
-                 split_partition=True, sdf_state=None):
+                 split_partition=True, sdf_state=None, tex_enc_cfg=None):
         import nvdiffrast.torch as dr
         from geometry.hmsdf import HmSDFTetsGeometry
         from render.mlptexture import MLPTexture3D
@@ -104,7 +104,7 @@ class Scene:
         t = lambda v: torch.tensor(v, dtype=torch.float32, device=device)
         mlp_min = torch.cat((t(F.kd_min)[0:3], t(F.ks_min)))
         mlp_max = torch.cat((t(F.kd_max)[0:3], t(F.ks_max)))
-        self.material = {'kd_ks': MLPTexture3D(self.geometry.getAABB(), channels=6, min_max=[mlp_min, mlp_max]).to(device), 'bsdf': 'pbr'}
+        self.material = {'kd_ks': MLPTexture3D(self.geometry.getAABB(), channels=6, min_max=[mlp_min, mlp_max], enc_cfg=tex_enc_cfg).to(device), 'bsdf': 'pbr'}
         mv, mvp, campos = synth.camera(res)
         self.mvp = torch.from_numpy(mvp).to(device)[None].expand(n_frames, -1, -1).contiguous()
         self.mv = torch.from_numpy(mv).to(device)[None].expand(n_frames, -1, -1).contiguous()

@@ -1,5 +1,8 @@
 """MLPTexture3D with the reference's interface (render/mlptexture.py:51-115): `.encoder.params`, `.net.net.{0,2,4}.weight`,
-`.sample(texc, frame_id)`.  sample() runs the fused grid-encoding + MLP kernel (csrc/texmlp.hip)."""
+`.sample(texc, frame_id)`.  For the reference's shape (its grid, 10 -> 32 -> 32 -> 6) sample() runs the fused grid-encoding + MLP kernel
+(csrc/texmlp.hip); with another `enc_cfg` or another `channels` / `internal_dims` / `hidden` it is the composed path of the reference
+itself (:91-107): box normalisation + clamp, `self.encoder` (csrc/gridenc.hip through the tinycudann shim), the x128 input-gradient
+scale of _MLP (:31), `self.net` through the library GEMMs, the sigmoid range map."""
 import numpy as np
 import torch
 import tinycudann as tcnn
@@ -26,23 +29,37 @@ class _MLP(torch.nn.Module):
         return y
 
 
+class _ScaleGrad(torch.autograd.Function):
+    """identity whose gradient is multiplied by `s`: the register_full_backward_hook of the reference's _MLP (mlptexture.py:31)"""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        ctx.s = s
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.s, None
+
+
 class MLPTexture3D(torch.nn.Module):
     # mlptexture.py:94: hard-coded, sign-flipped box; AABB and frame_id are ignored by the reference -- kept literally
     BBOX = (0.6, 0.6, 0.2, -0.8, -1.2, -0.2)
 
-    def __init__(self, AABB, channels=3, internal_dims=32, hidden=2, min_max=None, use_float16=False):
+    def __init__(self, AABB, channels=3, internal_dims=32, hidden=2, min_max=None, use_float16=False, enc_cfg=None):
         super().__init__()
         self.channels, self.internal_dims, self.AABB, self.min_max, self.use_float16 = channels, internal_dims, AABB, min_max, use_float16
         per_level_scale = np.exp(np.log(4096 / 16) / (16 - 1))
-        enc_cfg = {"otype": "HashGrid", "n_levels": 5, "n_features_per_level": 2, "log2_hashmap_size": 21, "base_resolution": 16,
-                   "per_level_scale": per_level_scale}
+        if enc_cfg is None:
+            enc_cfg = {"otype": "HashGrid", "n_levels": 5, "n_features_per_level": 2, "log2_hashmap_size": 21, "base_resolution": 16,
+                       "per_level_scale": per_level_scale}
         self.encoder = tcnn.Encoding(3, enc_cfg)
         self.net = _MLP({"n_input_dims": self.encoder.n_output_dims, "n_output_dims": channels, "n_hidden_layers": hidden,
                          "n_neurons": internal_dims}, 128.0)
         dev = self.encoder.params.device
         self.net.to(dev)
-        if channels != 6 or internal_dims != 32 or hidden != 2:
-            raise NotImplementedError('d3h MLPTexture3D: the fused kernel is built for the reference shape 10 -> 32 -> 32 -> 6')
+        # the fused kernel is built for the reference's grid and the shape 10 -> 32 -> 32 -> 6; everything else is composed (see sample())
+        self.fused = self.encoder.cfg is None and channels == 6 and internal_dims == 32 and hidden == 2
 
     def _range_host(self):
         """host copy of the output range (HOST arguments of the C ABI).  Read back once per value: a `.cpu()` here is a stream
@@ -60,9 +77,27 @@ class MLPTexture3D(torch.nn.Module):
         return hit[1]
 
     def sample(self, texc, frame_id=None, mask=None):
+        if not self.fused:
+            return self._sample_composed(texc, mask)
         w = [self.net.net[i].weight for i in (0, 2, 4)]
         omin, omax = self._range_host()
         return _T.texture_mlp(texc, self.encoder.params, w[0], w[1], w[2], self.BBOX, omin, omax, mask=mask, in_grad_scale=self.net.loss_scale)
+
+    def _sample_composed(self, texc, mask):
+        """mlptexture.py:91-107 op by op; rows with mask <= 0 are evaluated, then zeroed (no gradient flows through them)"""
+        dev = texc.device
+        b0 = torch.tensor(self.BBOX[:3], dtype=torch.float32, device=dev)
+        b1 = torch.tensor(self.BBOX[3:], dtype=torch.float32, device=dev)
+        x = torch.clamp((texc.reshape(-1, 3) - b0[None]) / (b1 - b0)[None], min=0, max=1)
+        enc = self.encoder(x.contiguous())
+        if self.net.loss_scale != 1.0:
+            enc = _ScaleGrad.apply(enc, self.net.loss_scale)
+        out = self.net(enc)
+        lo, hi = (torch.as_tensor(v, dtype=torch.float32, device=dev) for v in (self.min_max[0], self.min_max[1]))
+        out = torch.sigmoid(out) * (hi[None, :] - lo[None, :]) + lo[None, :]
+        if mask is not None:
+            out = out * (mask.reshape(-1, 1) > 0).to(out.dtype)
+        return out.reshape(*texc.shape[:-1], self.channels)
 
     def clamp_(self):
         pass

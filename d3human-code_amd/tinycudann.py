@@ -1,29 +1,38 @@
-"""Shim under the third-party name so `import tinycudann as tcnn` (render/mlptexture.py:11) resolves to csrc/texmlp.hip.
-Only what the reference uses: tcnn.Encoding(3, HashGrid cfg) with .params / .n_output_dims, and free_temporary_memory()."""
+"""Shim under the third-party name so `import tinycudann as tcnn` (render/mlptexture.py:11) resolves to the project's HIP kernels.
+
+tcnn.Encoding(n_input_dims, encoding_config) with .params / .n_input_dims / .n_output_dims / forward, and free_temporary_memory().
+  * the reference's configuration (render/mlptexture.py:68-75: 3-D HashGrid, 5 levels x 2 features, base 16, its per-level scale, a table
+    large enough that every level is dense) runs on csrc/texmlp.hip, as it always has (`cfg is None`);
+  * every other HashGrid / DenseGrid / Grid configuration runs on the general encoding of csrc/gridenc.hip (`cfg` = its
+    d3h.gridenc.GridConfig; the accepted keys, their defaults and the semantics are in the docstring of d3h/gridenc.py).
+The output is float32 (tcnn's default is half precision: a documented deviation); features are initialised U(-1e-4, 1e-4) from `seed`.
+tcnn.Network / NetworkWithInputEncoding are not built (the reference never constructs them)."""
 import torch
 
 from d3h import texmlp as _T
+from d3h import gridenc as _G
 
 
 class Encoding(torch.nn.Module):
     def __init__(self, n_input_dims, encoding_config, dtype=None, seed=1337):
         super().__init__()
         c = encoding_config
-        ok = (n_input_dims == 3 and c.get('otype') == 'HashGrid' and c.get('n_levels') == 5 and c.get('n_features_per_level') == 2
-              and c.get('base_resolution') == 16 and abs(c.get('per_level_scale') - _T.PER_LEVEL_SCALE) < 1e-9
-              and c.get('log2_hashmap_size', 21) >= 19)
-        if not ok:
-            raise NotImplementedError(f'd3h tinycudann shim: only the HashGrid of render/mlptexture.py:68-75 is built (got {c})')
-        self.n_input_dims = 3
-        self.n_output_dims = _T.ENC_DIMS
+        ref = (n_input_dims == 3 and c.get('otype') == 'HashGrid' and c.get('n_levels') == 5 and c.get('n_features_per_level') == 2
+               and c.get('base_resolution') == 16 and abs(c.get('per_level_scale', 2.0) - _T.PER_LEVEL_SCALE) < 1e-9
+               and c.get('log2_hashmap_size', 21) >= 19 and c.get('type', 'Hash') == 'Hash' and c.get('interpolation', 'Linear') == 'Linear')
+        self.cfg = None if ref else _G.GridConfig(n_input_dims, c)
+        self.n_input_dims = n_input_dims
+        self.n_output_dims = _T.ENC_DIMS if ref else self.cfg.n_output_dims
         dev = 'cuda' if torch.cuda.is_available() else 'cpu'
         g = torch.Generator().manual_seed(seed)
-        n = _T.grid_param_count()
+        n = _T.grid_param_count() if ref else self.cfg.n_params
         # tcnn initialises grid features U(-1e-4, 1e-4)
         self.params = torch.nn.Parameter(((torch.rand(n, generator=g) * 2 - 1) * 1e-4).to(dev))
 
     def forward(self, x):
-        return _T.grid_encode(x, self.params)
+        if self.cfg is None:
+            return _T.grid_encode(x, self.params)
+        return _G.grid_encode(x, self.params, self.cfg)
 
 
 def free_temporary_memory():
