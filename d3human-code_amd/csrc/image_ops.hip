@@ -10,6 +10,7 @@
 // All of these are HBM-streaming passes (O(10) flop per element): one coalesced sweep each, block-level reductions
 // (wave shuffles + one atomic per workgroup) for the scalar outputs.
 #include "d3h_vec.h"
+#include "d3h_bcast.h"
 #include "composite.h"
 
 namespace {
@@ -79,9 +80,7 @@ __global__ void face_normals_bwd_kernel(const float* __restrict__ v, const int* 
 }
 
 // ---- prepare_shading_normal -------------------------------------------------------------------------
-// inputs are [B,H,W,3] or broadcast along any of B/H/W (stride 0), as c_src/tensor.h:20-92 allows
-struct Bc { const float* p; long long sb, sh, sw; };
-__device__ __forceinline__ V3 fetch(const Bc& t, int b, int y, int x) { return ld3(t.p + b * t.sb + y * t.sh + x * t.sw); }
+// inputs are [B,H,W,3] or broadcast along any of B/H/W (stride 0): Bc / fetch of d3h_bcast.h
 
 constexpr float NORMAL_THRESHOLD = 0.1f;    // bsdf.py:13
 

@@ -71,7 +71,9 @@ def face_normals(v_pos, faces32):
 
 
 # ---- prepare_shading_normal ---------------------------------------------------------------------------
-def _bc_strides(ts, shape):
+def _bc_strides(ts, shape, what='prepare_shading_normal'):
+    """ts: tensors [B,H,W,C] or broadcast along any of B / H / W (fewer than four dims: leading ones are added) -> (float32 contiguous copies,
+    int64[len(ts)][3] of their (b, h, w) element strides with 0 for a broadcast dim): the `Bc` convention of csrc/d3h_bcast.h"""
     B, H, W = shape
     out = []
     keep = []
@@ -84,9 +86,9 @@ def _bc_strides(ts, shape):
         st = [t.stride(k) if t.shape[k] != 1 else 0 for k in range(3)]
         for k, full in enumerate((B, H, W)):
             if t.shape[k] not in (1, full):
-                raise RuntimeError('prepare_shading_normal: shapes are not broadcastable')
+                raise RuntimeError(f'{what}: shapes are not broadcastable')
         out += st
-    arr = (ctypes.c_int64 * 18)(*out)
+    arr = (ctypes.c_int64 * len(out))(*out)
     return keep, arr
 
 

@@ -1,14 +1,19 @@
-"""render.renderutils with the reference's entry points (render/renderutils/ops.py:197,479,518,541) on the HIP kernels.
-The BSDF / cubemap functions of the reference plugin are dead under the hard-wired bsdf='kd' (render/render.py:120) and are
-not provided."""
+"""render.renderutils with every entry point the reference's render/renderutils/__init__.py exports, on the HIP kernels:
+xfm_points, xfm_vectors, image_loss, prepare_shading_normal (ops.py:197,479,518,541: the ones the training loop calls); the per-pixel BSDF
+functions lambert, frostbite_diffuse, pbr_specular, pbr_bsdf and the four test entry points _fresnel_shlick, _ndf_ggx, _lambda_ggx,
+_masking_smith (ops.py:92-389; csrc/bsdf.hip); the environment-map filters diffuse_cubemap, specular_cubemap (ops.py:394-461; csrc/cubemap.hip).
+The BSDF and cube-map functions are dead under the reference's hard-wired bsdf='kd' (render/render.py:120); they are here for code that shades
+with a point light or a split-sum environment light.  `use_python=True` selects this package's own torch composition of the same formulas
+(d3h/bsdf.py: py_*) where there is one; the cube-map filters have none, as in the reference."""
 import logging
 import os
 
 import torch
 
-from d3h import imgops as _I
+from d3h import bsdf as _B, cubemap as _C, imgops as _I
 
-__all__ = ['xfm_points', 'xfm_vectors', 'image_loss', 'prepare_shading_normal']
+__all__ = ['xfm_points', 'xfm_vectors', 'image_loss', 'prepare_shading_normal', 'lambert', 'frostbite_diffuse', 'pbr_specular', 'pbr_bsdf',
+           '_fresnel_shlick', '_ndf_ggx', '_lambda_ggx', '_masking_smith', 'diffuse_cubemap', 'specular_cubemap']
 
 
 def xfm_points(points, matrix, use_python=True):
@@ -84,3 +89,58 @@ def loss_spec(loss_fn, device):
 
 def prepare_shading_normal(pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm, two_sided_shading=True, opengl=True, use_python=False):
     return _I.prepare_shading_normal(pos, view_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm, two_sided_shading, opengl)
+
+
+# ---- per-pixel BSDF functions: tensors are [B,H,W,C] or a broadcastable equivalent (ops.py:92-389) ------------------------------------
+def _finite(out, name):
+    if torch.is_anomaly_enabled():
+        assert torch.all(torch.isfinite(out)), f"Output of {name} contains inf or NaN"
+    return out
+
+
+def _fresnel_shlick(f0, f90, cosTheta, use_python=False):
+    return _finite((_B.py_fresnel_shlick if use_python else _B.fresnel_shlick)(f0, f90, cosTheta), '_fresnel_shlick')
+
+
+def _ndf_ggx(alphaSqr, cosTheta, use_python=False):
+    return _finite((_B.py_ndf_ggx if use_python else _B.ndf_ggx)(alphaSqr, cosTheta), '_ndf_ggx')
+
+
+def _lambda_ggx(alphaSqr, cosTheta, use_python=False):
+    return _finite((_B.py_lambda_ggx if use_python else _B.lambda_ggx)(alphaSqr, cosTheta), '_lambda_ggx')
+
+
+def _masking_smith(alphaSqr, cosThetaI, cosThetaO, use_python=False):
+    return _finite((_B.py_masking_smith if use_python else _B.masking_smith)(alphaSqr, cosThetaI, cosThetaO), '_masking_smith')
+
+
+def lambert(nrm, wi, use_python=False):
+    """Lambertian lobe max(n . wi, 0) / pi -> [B,H,W,1]"""
+    return _finite((_B.py_lambert if use_python else _B.lambert)(nrm, wi), 'lambert')
+
+
+def frostbite_diffuse(nrm, wi, wo, linearRoughness, use_python=False):
+    """Frostbite's normalised Disney diffuse lobe -> [B,H,W,1]"""
+    return _finite((_B.py_frostbite_diffuse if use_python else _B.frostbite_diffuse)(nrm, wi, wo, linearRoughness), 'frostbite_diffuse')
+
+
+def pbr_specular(col, nrm, wo, wi, alpha, min_roughness=0.08, use_python=False):
+    """GGX specular lobe (Schlick Fresnel, Smith correlated masking); alpha [B,H,W,1] -> [B,H,W,3]"""
+    return _finite((_B.py_pbr_specular if use_python else _B.pbr_specular)(col, nrm, wo, wi, alpha, min_roughness), 'pbr_specular')
+
+
+def pbr_bsdf(kd, arm, pos, nrm, view_pos, light_pos, min_roughness=0.08, bsdf="lambert", use_python=False):
+    """Diffuse + specular lobes for a point light: kd albedo, arm = (specular attenuation, linear roughness, metalness), pos / nrm the g-buffer,
+    view_pos / light_pos typically broadcast; bsdf: the diffuse lobe, 'lambert' or 'frostbite' -> [B,H,W,3]"""
+    return _finite((_B.py_pbr_bsdf if use_python else _B.pbr_bsdf)(kd, arm, pos, nrm, view_pos, light_pos, min_roughness, bsdf == 'frostbite'), 'pbr_bsdf')
+
+
+# ---- cube-map filters with filtering across edges (ops.py:394-461) --------------------------------------------------------------------
+def diffuse_cubemap(cubemap, use_python=False):
+    assert not use_python, 'diffuse_cubemap has no torch composition'
+    return _finite(_C.diffuse_cubemap(cubemap), 'diffuse_cubemap')
+
+
+def specular_cubemap(cubemap, roughness, cutoff=0.99, use_python=False):
+    assert not use_python, 'specular_cubemap has no torch composition'
+    return _finite(_C.specular_cubemap(cubemap, roughness, cutoff), 'specular_cubemap')
