@@ -106,8 +106,8 @@ def save_ckp(FLAGS, save_path, it, geometry, mat, lgt=None):
 
 def load_ckp(FLAGS, save_path, geometry, mat, stage, last=None, device=None):
     """train.py:292-331: `last` defaults to FLAGS.<stage>_epoch - 1.  Returns (geometry, mat, lgt) as the reference; lgt is the probe loaded
-    through render.light.load_env when that module (the reference's, further down the module path) is importable, else None -- the light
-    is unused under bsdf = 'kd'."""
+    through render.light.load_env -- on a host that can run the product: the light's tables are built by a kernel (csrc/envlight.hip), so
+    without a GPU lgt is None (geometry, material and pose still load)."""
     if last is None:
         last = {'init': getattr(FLAGS, 'init_epoch', 1), 'split': getattr(FLAGS, 'split_epoch', 1), 'fine': getattr(FLAGS, 'fine_epoch', 1)}[stage] - 1
     d = os.path.join(save_path, stage, 'ckp')
@@ -121,10 +121,8 @@ def load_ckp(FLAGS, save_path, geometry, mat, stage, last=None, device=None):
     lgt = None
     probe = os.path.join(d, 'probe_{}.hdr'.format(last))
     if os.path.exists(probe):
-        try:
+        from . import _lib as L
+        if torch.cuda.is_available() or L.emulated():          # a corrupt probe is an error, not a silent None
             from render import light
-        except ImportError:                  # the reference's render/light.py is not on the path: the light is unused under bsdf = 'kd'
-            light = None
-        if light is not None:                # a corrupt probe is an error, not a silent None
             lgt = light.load_env(probe, scale=getattr(FLAGS, 'env_scale', 1.0), res=[getattr(FLAGS, 'probe_res', 16)] * 2)
     return geometry, mat, lgt

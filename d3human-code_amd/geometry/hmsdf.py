@@ -449,6 +449,12 @@ class HmSDFTetsGeometry(torch.nn.Module):
         if 'sampled_pts' not in d:
             self._launch_eikonal(d, opt_mesh, target)
         idx0 = target['idx'][0] if isinstance(target['idx'], (list, tuple)) else target['idx']
+        if _flag(self.FLAGS, 'lit_shading', False):
+            # the mesh the shadow rays are traced against is the posed mesh about to be rendered (the reference's last optix_build_bvh of every
+            # getMesh_*, hmsdf.py:481,592,698).  Recording is free; the BVH is built only if the bsdf traces rays.  The watertight twin below is
+            # traced against the same record: it reuses the BVHs this render built (also the per-frame ones, kept on the context) and, being a
+            # shade of its own, takes the next rnd_seed, as in the reference
+            ou.optix_build_bvh(self.optix_ctx, opt_mesh.v_pos, opt_mesh.t_pos_idx32, rebuild=1)
         d['buffers'] = render.render_mesh(self.FLAGS, idx0, glctx, opt_mesh, original_mesh, target['mvp'], target['campos'], lgt,
                                           target['resolution'], spp=target['spp'], msaa=True, background=target['background'], bsdf=bsdf,
                                           use_uv=use_uv, optix_ctx=self.optix_ctx, denoiser=denoiser, shadow_scale=shadow_scale,
@@ -640,6 +646,8 @@ class HmSDFTetsGeometry(torch.nn.Module):
         d = self.getMesh_seq(opt_material, target=target, it=iteration, save_tmp=True, t=t)
         all_mesh = d['all_mesh']
         idx0 = target['idx'][0] if isinstance(target['idx'], (list, tuple)) else target['idx']
+        if _flag(self.FLAGS, 'lit_shading', False):
+            ou.optix_build_bvh(self.optix_ctx, all_mesh.v_pos, all_mesh.t_pos_idx32, rebuild=1)          # as in _render
         d['all_mesh_buffers'] = render_mask.render_mesh(self.FLAGS, idx0, glctx, all_mesh, d['tmp_nodeform_mesh'], target['mvp'], target['campos'],
                                                         lgt, target['resolution'], spp=target['spp'], msaa=True, background=target['background'],
                                                         bsdf=bsdf, use_uv=use_uv, optix_ctx=self.optix_ctx, denoiser=denoiser,

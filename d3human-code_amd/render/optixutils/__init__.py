@@ -17,11 +17,13 @@ _random_perm = {}                           # n_samples_x -> [32768, n_samples_x
 
 
 class OptiXContext:
-    """Holds the mesh given to optix_build_bvh (`pending`) and the BVH built from it (`bvh`)."""
+    """Holds the mesh given to optix_build_bvh (`pending`) and the BVH built from it (`bvh`); `frames`: (the record, one context per posed frame) when
+    render_mesh traced a batch of posed meshes against it (render.render._frame_contexts)."""
 
     def __init__(self):
         self.pending = None
         self.bvh = None
+        self.frames = None
 
     def build(self):
         """Build now what optix_build_bvh recorded -- for callers that overwrite the tensors before they shade."""
@@ -40,6 +42,7 @@ def optix_build_bvh(optix_ctx, verts, tris, rebuild):
     that overwrites them in place in between calls optix_ctx.build() first.  Both values of `rebuild` mean "rebuild at next use" (there is no
     refit in place of a rebuild); a second call before use replaces the first.  An empty mesh is a valid scene in which nothing is occluded."""
     optix_ctx.pending = (verts, tris)
+    optix_ctx.frames = None
 
 
 def optix_env_shade(optix_ctx, mask, ro, gb_pos, gb_normal, gb_view_pos, gb_kd, gb_ks, light, pdf, rows, cols, BSDF='pbr', n_samples_x=8, rnd_seed=None,

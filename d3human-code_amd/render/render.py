@@ -7,6 +7,11 @@ HBM: attributes sharing an index buffer are interpolated in ONE pass, the textur
 buffers are composited and antialiased in ONE pass over a channel-concatenated image (antialias is per-channel linear, so this is
 exact).  `buffers=` (an extension; default = all, as the reference) lets a caller name the outputs it will read.
 
+FLAGS.lit_shading (an extension, off by default) makes the branch of render.py:121-163 real, which the reference's hard-wired `bsdf = 'kd'`
+(render.py:120) leaves dead: the environment light sampled with shadow rays against the posed mesh (render.optixutils), the denoiser, the
+PBR / diffuse / white combine -- `shade_lit`.  Without the flag nothing of it is touched: `lgt`, `optix_ctx`, `bsdf`, `denoiser` and
+`shadow_scale` are accepted and ignored, as before.
+
 `mesh.v_pos` may be [P,3] (the reference) or [B,P,3] (one posed mesh per frame of the batch: the build's N-frame extension,
 SURVEY F5).  spp > 1 is not part of the hot path (FLAGS.spp = 1) and raises.
 """
@@ -18,10 +23,15 @@ import nvdiffrast.torch as dr
 
 from . import util
 from . import renderutils as ru
+from . import optixutils as ou
 from d3h import imgops as _I
 from d3h import raster as _R
 
 ALL_BUFFERS = ('shaded', 'z_grad', 'normal', 'geometric_normal', 'kd', 'ks', 'kd_grad', 'ks_grad', 'normal_grad', 'depth', 'invdepth')
+LIT_BUFFERS = ('diffuse_light', 'specular_light')          # render.py:197-200: present only when the lit branch ran
+LIT_BSDFS = ('pbr', 'diffuse', 'white')
+BSDFS = ('kd', 'ks', 'normal', 'tangent') + LIT_BSDFS
+rnd_seed = 0                                               # render.py:128-132: the sampler's seed, one step per lit shade
 
 
 class LazyVisibleTriangles(torch.Tensor):
@@ -68,9 +78,79 @@ def _batched(v):
     return v if v.dim() == 3 else v[None]
 
 
+def shade_lit(FLAGS, cover, ro, gb_pos, gb_normal, zdz, view_pos, kd, ks, lgt, optix_ctx, bsdf, denoiser, shadow_scale=1.0):
+    """render.py:121-163: the lit colour of bsdf 'pbr' / 'diffuse' / 'white' -> {'shaded', 'diffuse_light', 'specular_light'}, each [B,H,W,3].
+
+    cover [B,H,W] or [B,H,W,1] (> 0: shade this pixel); ro = gb_pos + 0.001 n, the shadow rays' origin; gb_normal the prepared shading normal;
+    zdz [B,H,W,2] = (z, |dz|), the denoiser's depth guide (read only when a denoiser is given); view_pos broadcastable to gb_pos.  `optix_ctx` is
+    one OptiXContext for the whole batch or a list of B, one per frame: then frame b is traced against context b alone (B launches on [1,H,W]
+    slices, all with the call's seed).  The seed is the module's `rnd_seed`, which advances by one per call; FLAGS.decorrelated passes None (a fresh
+    seed each way).  With FLAGS.denoiser_demodulate the two light images are denoised (under one set of guides: one launch each way when the
+    denoiser has `forward_many`) before the combine, else the combined colour is.  The reference's debug image writes are not reproduced."""
+    global rnd_seed
+    from . import light
+    if bsdf not in LIT_BSDFS:
+        raise RuntimeError(f"shade_lit: bsdf must be one of {LIT_BSDFS}, got {bsdf!r}")
+    if not isinstance(lgt, light.EnvironmentLight) or optix_ctx is None:
+        raise RuntimeError('shade_lit: lit shading needs an EnvironmentLight and an OptiXContext')
+    if bsdf == 'white':
+        kd = torch.ones_like(kd)
+    seed = None if getattr(FLAGS, 'decorrelated', False) else rnd_seed
+    rnd_seed += 1
+    view = view_pos.expand(gb_pos.shape)
+    tables = (lgt.base, lgt._pdf, lgt.rows[:, 0], lgt.cols)
+    kw = dict(BSDF=bsdf, n_samples_x=getattr(FLAGS, 'n_samples', 4), rnd_seed=seed, shadow_scale=shadow_scale)
+    ctxs = list(optix_ctx) if isinstance(optix_ctx, (list, tuple)) else [optix_ctx]
+    if len(ctxs) == 1:
+        diffuse, specular = ou.optix_env_shade(ctxs[0], cover, ro, gb_pos, gb_normal, view, kd, ks, *tables, **kw)
+    else:
+        if len(ctxs) != gb_pos.shape[0]:
+            raise RuntimeError(f'shade_lit: {len(ctxs)} contexts for {gb_pos.shape[0]} frames')
+        f = lambda t, b: t[b:b + 1]
+        per = [ou.optix_env_shade(c, f(cover, b), f(ro, b), f(gb_pos, b), f(gb_normal, b), f(view, b), f(kd, b), f(ks, b), *tables, **kw)
+               for b, c in enumerate(ctxs)]
+        diffuse, specular = torch.cat([d for d, _ in per], dim=0), torch.cat([s_ for _, s_ in per], dim=0)
+    demodulate = getattr(FLAGS, 'denoiser_demodulate', True)
+    if denoiser is not None and demodulate:
+        if hasattr(denoiser, 'forward_many'):
+            diffuse, specular = denoiser.forward_many([diffuse, specular], gb_normal, zdz)
+        else:
+            diffuse = denoiser.forward(torch.cat((diffuse, gb_normal, zdz), dim=-1))
+            specular = denoiser.forward(torch.cat((specular, gb_normal, zdz), dim=-1))
+    if bsdf == 'pbr':
+        shaded = diffuse * (kd * (1.0 - ks[..., 2:3])) + specular          # kd (1 - metalness)
+    else:
+        shaded = diffuse * kd
+    if denoiser is not None and not demodulate:
+        shaded = denoiser.forward(torch.cat((shaded, gb_normal, zdz), dim=-1))
+    return {'shaded': shaded, 'diffuse_light': diffuse, 'specular_light': specular}
+
+
+def _frame_contexts(optix_ctx, B):
+    """The contexts a batch of B frames is traced against.  optix_build_bvh recorded the posed mesh; with one posed mesh per frame (vertices
+    [B,P,3]) every frame gets a context of its own over ITS vertices -- built lazily, like any other -- where OptiXContext.build() would flatten
+    the batch into one soup and test every frame against all of them at frame 0's indices.  The B contexts are kept on `optix_ctx.frames` beside the
+    record they were made from: a second render_mesh against the same record (the watertight twin of geometry.hmsdf._render) reuses their BVHs, as a
+    single context reuses its own; the next optix_build_bvh replaces the record and with it the contexts."""
+    pend = None if optix_ctx is None else optix_ctx.pending
+    if B == 1 or pend is None or pend[0].dim() != 3 or pend[0].shape[0] != B:
+        return optix_ctx
+    if optix_ctx.frames is not None and optix_ctx.frames[0] is pend:
+        return optix_ctx.frames[1]
+    verts, tris = pend
+    ctxs = []
+    for b in range(B):
+        c = ou.OptiXContext()
+        ou.optix_build_bvh(c, verts[b], tris if tris.dim() == 2 else tris[b], rebuild=1)
+        ctxs.append(c)
+    optix_ctx.frames = (pend, ctxs)
+    return ctxs
+
+
 def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, gb_normal, gb_tangent, view_pos, material, want,
-          finetune_normal=True, mask=None, rng_draws=None, live=None, skip_uncovered=True):
-    """render.py:42-205 restricted to the live branch (bsdf == 'kd', perturbed_nrm is None).  `aux` = (z_grad values, depth, invdepth) from
+          finetune_normal=True, mask=None, rng_draws=None, live=None, skip_uncovered=True, lit=None):
+    """render.py:42-205 with perturbed_nrm None.  `lit` None: the branch the reference's hard-wired bsdf = 'kd' leaves live, exactly; else
+    (bsdf, lgt, contexts, denoiser, shadow_scale) of FLAGS.lit_shading: 'shaded' follows the bsdf (render.py:121-176).  `aux` = (z_grad values, depth, invdepth) from
     the fused forward-only pass (d3h.raster.aux_buffers; entries None where not produced); `live`: the buffers that need a gradient
     (None = all) -- the producers of the others run under torch.no_grad()."""
     B, H, W = rast.shape[:3]
@@ -148,7 +228,20 @@ def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, g
         with on('normal'):
             out['normal'] = ru.prepare_shading_normal(gb_pos, view_pos, None, gb_normal, gb_tangent, gb_geometric_normal, two_sided_shading=True,
                                                       opengl=True)
-    if 'shaded' in want:
+    if 'shaded' in want and lit is not None:
+        bsdf, lgt, ctxs, denoiser, shadow_scale = lit
+        with on('shaded'):
+            if bsdf in LIT_BSDFS:
+                n = out['normal']
+                out.update(shade_lit(FLAGS, mask, gb_pos + n * 0.001, gb_pos, n, aux[0][..., 0:2] if denoiser is not None else None, view_pos, kd, ks,
+                                     lgt, ctxs, bsdf, denoiser, shadow_scale))
+            elif bsdf == 'normal':
+                out['shaded'] = (out['normal'] + 1.0) * 0.5        # render.py:165-174
+            elif bsdf == 'tangent':
+                out['shaded'] = (gb_tangent + 1.0) * 0.5
+            else:
+                out['shaded'] = kd if bsdf == 'kd' else ks
+    elif 'shaded' in want:
         out['shaded'] = kd                                         # bsdf = 'kd' (render.py:120,169-170)
         if not fused:
             out['_shaded_of'] = all_tex                            # kd IS all_tex[..., :3]: the fused composite takes the wide tensor (compose)
@@ -195,6 +288,25 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
         want.add('msdf_image')
     grad_on = torch.is_grad_enabled()
     live = None if (_grad_buffers is None or not grad_on) else (want & set(_grad_buffers))
+    # ---- FLAGS.lit_shading: the colour follows the bsdf (render.py:117-176).  `want` grows by what the lit colour is made of, so that a caller that
+    # reads only 'shaded' still gets positions, shading normal, kd / ks and the denoiser's (z, |dz|); `want_out` / `live_out` stay what was asked for
+    want_out, live_out, lit = set(want), live, None
+    if getattr(FLAGS, 'lit_shading', False):
+        assert bsdf is not None or 'bsdf' in mesh.material, 'Material must specify a BSDF type'
+        bsdf = mesh.material['bsdf'] if bsdf is None else bsdf
+        if bsdf not in BSDFS:
+            raise RuntimeError(f"render_mesh: invalid BSDF '{bsdf}'")
+        if buffers is None and bsdf in LIT_BSDFS:
+            want_out |= set(LIT_BUFFERS)
+        if 'shaded' in want:
+            deps = {'pbr': {'normal', 'kd', 'ks'}, 'diffuse': {'normal', 'kd', 'ks'}, 'white': {'normal', 'kd', 'ks'}, 'normal': {'normal'},
+                    'tangent': {'normal'}, 'kd': {'kd'}, 'ks': {'ks'}}[bsdf]
+            if bsdf in LIT_BSDFS and denoiser is not None:
+                deps = deps | {'z_grad'}
+            want = want | deps
+            if live is not None and 'shaded' in live:
+                live = live | (deps - {'z_grad'})
+            lit = (bsdf, lgt, None, denoiser, shadow_scale)
     view_pos = view_pos[:, None, None, :] if view_pos.dim() == 2 else view_pos
     tri = mesh.t_pos_idx32
     dev = mesh.v_pos.device
@@ -258,8 +370,13 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
         aux = _R.aux_buffers(v_pos_clip, rast, db, tri, gb_pos, view_pos, want_z='z_grad' in want, want_depth=no_grad_of('depth'),
                              want_invdepth=no_grad_of('invdepth'))
 
+    if lit is not None and lit[0] in LIT_BSDFS:
+        lit = (lit[0], lit[1], _frame_contexts(optix_ctx, B), lit[3], lit[4])
     layer = shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, gb_normal, gb_tangent, view_pos, mesh.material,
-                  want, finetune_normal, mask=cover, rng_draws=_rng_draws, live=live, skip_uncovered=(H, W) == (Hf, Wf))
+                  want, finetune_normal, mask=cover, rng_draws=_rng_draws, live=live, skip_uncovered=(H, W) == (Hf, Wf), lit=lit)
+    if lit is not None:
+        layer = {k: t for k, t in layer.items() if k in want_out}              # what the lit colour was made of is not an output unless asked for
+        want, live = want_out, live_out
     shaded_of = layer.pop('_shaded_of', None)
     if (H, W) != (Hf, Wf):
         shaded_of = None
@@ -299,24 +416,27 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
             img = dr.antialias(_I.composite(rast_full, sources), rast_full, v_pos_clip, tri)
         return (util.avg_pool_nhwc(img, spp) if spp > 1 else img), widths                              # render.py:449
 
-    all_keys = [k for k in list(ALL_BUFFERS) + ['msdf_image'] if k in layer]
+    all_keys = [k for k in list(ALL_BUFFERS) + ['msdf_image'] + list(LIT_BUFFERS) if k in layer]
     live_keys = all_keys if live is None else [k for k in all_keys if k in live]
     dead_keys = [k for k in all_keys if k not in live_keys]
     # '_stacked' / '_layout': the channel-concatenated image itself, for consumers that read several buffers in one pass
     # (d3h.imgops.pixel_losses); the per-buffer entries are views of it, as the reference's separate tensors would be
     out_buffers = {'_layout': {}}
     for name, keys, no_grad in (('_stacked', live_keys, False), ('_stacked_nograd', dead_keys, True)):
-        if not keys:
-            continue
-        with torch.set_grad_enabled(grad_on and not no_grad):
-            stacked, widths = compose(keys)
-        out_buffers[name] = stacked
-        c0 = 0
-        for k, n in zip(keys, widths):
-            out_buffers[k] = stacked[..., c0:c0 + n]
-            if not no_grad:
-                out_buffers['_layout'][k] = (c0, n)
-            c0 += n
+        # (the composite pass takes 12 sources: the reference's 11 buffers and the msdf image fit; the two light images of the lit branch, last in the
+        # order, may overflow into a pass of their own, outside '_stacked' / '_layout', which no consumer of the layout reads them from)
+        for first in range(0, len(keys), 12):
+            chunk = keys[first:first + 12]
+            with torch.set_grad_enabled(grad_on and not no_grad):
+                stacked, widths = compose(chunk)
+            if first == 0:
+                out_buffers[name] = stacked
+            c0 = 0
+            for k, n in zip(chunk, widths):
+                out_buffers[k] = stacked[..., c0:c0 + n]
+                if not no_grad and first == 0:
+                    out_buffers['_layout'][k] = (c0, n)
+                c0 += n
     if '_stacked' not in out_buffers:
         out_buffers['_stacked'] = None
     if _keep_rast:

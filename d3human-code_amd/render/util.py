@@ -347,7 +347,13 @@ def save_image(fn, x):
 def load_image_raw(fn):
     if fn.endswith('.npy'):
         return np.load(fn)
-    import imageio
+    try:
+        import imageio
+    except ImportError:
+        if os.path.splitext(fn)[1].lower() == '.hdr':          # without an image library: the Radiance reader the checkpoints already use
+            from d3h.checkpoint import read_hdr
+            return read_hdr(fn)
+        raise
     return imageio.imread(fn)
 
 

@@ -20,7 +20,8 @@ GROUPS = {
     'cubemap.hip': 'render/renderutils/c_src/cubemap.cu:110-169 (diffuse_cubemap_{fwd,bwd}), :246-350 (specular_cubemap_{fwd,bwd}) as driven by render/renderutils/ops.py:394-461; the backward as a gather',
     'bvh.hip': 'render/optixutils/c_src/optix_wrapper.cpp (optix_build_bvh: the OptiX acceleration structure) and the optixTrace of c_src/envsampling/kernel.cu:101-118 (any-hit shadow ray): a linear BVH built on the device and a stackless any-hit traversal -- the occlusion query is an entry point of its own',
     'envshade.hip': 'render/optixutils/c_src/envsampling/kernel.cu:463-542 (__raygen__rg: importance-sampled environment shading with shadow rays) + torch_bindings.cpp (env_shade_{fwd,bwd}), shaded with c_src/bsdf.h; driven by render/optixutils/ops.py:81-108',
-    'denoise.hip': 'render/optixutils/c_src/denoising.cu:14-130 (bilateral_denoiser_{fwd,bwd}_kernel) as driven by render/optixutils/ops.py:110-122,145-147',
+    'denoise.hip': 'render/optixutils/c_src/denoising.cu:14-130 (bilateral_denoiser_{fwd,bwd}_kernel) as driven by render/optixutils/ops.py:110-122,145-147; a two-image form for the demodulated path of render/render.py:134-136 (one set of guides)',
+    'envlight.hip': 'render/light.py:46-59 (EnvironmentLight.update_pdf: the pdf of the lat-long map and the row / column CDFs the light sampler of envshade.hip searches)',
     'mesh_ops.hip': 'seq-stage mesh terms: render/mesh.py:30-82 (compute_laplacian_uniform) + lap_loss.py:40-47 (body_laplacian_loss), render/mesh.py:18-28,266-279 (normal_consistency_loss), geometry/hmsdf.py:98-132 (collision_loss); start-up: geometry/hmsdf.py:236-237 (pysdf.SDF of the SMPL-X template on the grid vertices)',
     'optim.hip': 'the optimiser step: train.py:747-748 (encoder gradient / 8), :759-768 (the two torch.optim.Adam steps of train.py:593-620), :788 + geometry/hmsdf.py:398-405 (clamp_deform)',
     'timing.hip': 'measurement only: per-launch HIP-event timing of selected kernels for bench.py (no reference counterpart; train.py:679,789-790 times whole iterations with time.time())',
@@ -28,7 +29,7 @@ GROUPS = {
     'fusedmlp.hip': 'tiny-cuda-nn Network (FullyFusedMLP / CutlassMLP; un-vendored) and the _MLP of render/mlptexture.py:18-41,100-103 for every shape texmlp.hip does not build: a bias-free MLP of 1..8 hidden layers of 16 / 32 / 64 / 128 neurons, seven activations, row mask, affine output map, forward and backward in one kernel each',
     'texmlp.hip': 'render/mlptexture.py:91-107 (MLPTexture3D.sample): tiny-cuda-nn HashGrid encoding (:62-79, un-vendored) + _MLP (:18-41) + sigmoid range map',
 }
-ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'envshade.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'optim.hip', 'timing.hip']
+ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'envshade.hip', 'envlight.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'optim.hip', 'timing.hip']
 head = '''/* d3h.h -- C ABI of libd3h_hip.so: the MI355X (gfx950) hot path of D3-Human's render-and-fit loop.
  * GENERATED by tools/gen_header.py from the extern "C" definitions in d3human-code_amd/csrc/ -- do not edit by hand.
  *
