@@ -1,0 +1,35 @@
+"""Textured-mesh export: a fitted mesh with its MLP material -> a mesh with uv coordinates and kd / ks / normal texture maps that
+render/obj.py:write_obj writes as mesh.obj + mesh.mtl + three PNGs (the reference's xatlas_uvmap, train.py:198-246).
+
+The chart is the closed-form triangle-pair atlas of d3h.uvatlas, the bake evaluates the material once per texel at the position of the
+owning triangle's affine map (gutter texels included, so nothing is dilated), and a level-0 bilinear lookup anywhere on the surface reads
+texels of its own triangle only.  The maps are for level-0 bilinear use (mip levels above 0 mix triangles); (s - 4)^2 / s^2 of the texels of
+a cell carry surface.  `render.render.render_uv` is the rasterising route of the reference and stays as a cross-check."""
+import torch
+
+from render import mesh as _mesh, texture as _texture
+from . import uvatlas as _U
+
+
+@torch.no_grad()
+def textured_mesh(mesh, material, texture_res, kd_min, kd_max, ks_min, ks_max, nrm_min, nrm_max):
+    """mesh: render.mesh.Mesh (v_pos [V,3], or [B,V,3] posed frames of which the first is baked); material: dict with 'kd_ks', an MLPTexture3D
+    of 6 channels; texture_res: (H, W) or one int.  -> Mesh(v_tex, t_tex_idx, base=mesh) whose material is `material` without 'kd_ks' and with
+    'kd', 'ks', 'normal' as trainable Texture2D ([1,H,W,3] each) clamped to the given ranges; texels no triangle owns hold the mean of the owned ones."""
+    v_pos = mesh.v_pos[0] if mesh.v_pos.dim() == 3 else mesh.v_pos
+    atlas = _U.make_atlas(v_pos, mesh.t_pos_idx, texture_res)
+    pos, owned, _, _ = _U.bake_positions(atlas, v_pos, mesh.t_pos_idx)
+    tex = material['kd_ks'].sample(pos, mask=owned)
+    assert tex.shape[-1] == 6, 'Combined kd_ks must be 6 channels'
+    mean = (tex * owned).sum(dim=(0, 1, 2)) / owned.sum().clamp(min=1.0)
+    tex = torch.where(owned > 0, tex, mean.expand_as(tex))
+    normal = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=tex.device).expand(*tex.shape[:3], 3)
+    dev = tex.device
+    rng = lambda lo, hi: [torch.as_tensor(lo, dtype=torch.float32, device=dev), torch.as_tensor(hi, dtype=torch.float32, device=dev)]
+    leaf = lambda t: t.clone().detach().contiguous().requires_grad_(True)
+    out = _mesh.Mesh(v_tex=atlas.uvs, t_tex_idx=atlas.t_tex_idx, base=mesh)
+    out.material = {k: v for k, v in material.items() if k != 'kd_ks'}
+    out.material.update({'kd': _texture.Texture2D(leaf(tex[..., 0:3]), min_max=rng(kd_min, kd_max)),
+                         'ks': _texture.Texture2D(leaf(tex[..., 3:6]), min_max=rng(ks_min, ks_max)),
+                         'normal': _texture.Texture2D(leaf(normal), min_max=rng(nrm_min, nrm_max))})
+    return out

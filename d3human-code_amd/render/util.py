@@ -321,6 +321,57 @@ def _png_bytes(a):
     return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, ctype, 0, 0, 0)) + chunk(b'IDAT', zlib.compress(raw, 3)) + chunk(b'IEND', b'')
 
 
+def _png_read(fn):
+    """8-bit greyscale / grey + alpha / RGB / RGBA PNG without interlacing -> uint8 [H,W] or [H,W,C] (what _png_bytes and the usual encoders write)"""
+    import struct
+    import zlib
+    with open(fn, 'rb') as f:
+        data = f.read()
+    if data[:8] != b'\x89PNG\r\n\x1a\n':
+        raise ValueError('%s is not a PNG file' % fn)
+    at, idat, head = 8, [], None
+    while at + 8 <= len(data):
+        n, tag = struct.unpack('>I4s', data[at:at + 8])
+        body = data[at + 8:at + 8 + n]
+        at += 12 + n
+        if tag == b'IHDR':
+            head = struct.unpack('>IIBBBBB', body)
+        elif tag == b'IDAT':
+            idat.append(body)
+        elif tag == b'IEND':
+            break
+    w, h, depth, ctype, _, _, interlace = head
+    if depth != 8 or ctype not in (0, 2, 4, 6) or interlace:
+        raise ValueError('%s: only 8-bit non-interlaced grey / RGB (+ alpha) PNGs are read without an image library' % fn)
+    c = {0: 1, 2: 3, 4: 2, 6: 4}[ctype]
+    raw = np.frombuffer(zlib.decompress(b''.join(idat)), np.uint8).reshape(h, 1 + w * c)
+    out = np.zeros((h, w * c), np.uint8)
+    zero = np.zeros(w * c, np.uint8)
+    for r in range(h):
+        kind, line = int(raw[r, 0]), raw[r, 1:]
+        up = out[r - 1] if r else zero
+        if kind == 0:
+            out[r] = line
+        elif kind == 2:
+            out[r] = line + up
+        else:                                            # Sub / Average / Paeth depend on the pixel to the left: byte by byte
+            cur, upi, li = [0] * (w * c), up.tolist(), line.tolist()
+            for k in range(w * c):
+                a, b, cc = (cur[k - c] if k >= c else 0), upi[k], (upi[k - c] if k >= c else 0)
+                if kind == 1:
+                    pred = a
+                elif kind == 3:
+                    pred = (a + b) >> 1
+                elif kind == 4:
+                    pa, pb, pc = abs(b - cc), abs(a - cc), abs(a + b - 2 * cc)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else cc)
+                else:
+                    raise ValueError('%s: unknown PNG filter %d' % (fn, kind))
+                cur[k] = (li[k] + pred) & 255
+            out[r] = cur
+    return out.reshape(h, w) if c == 1 else out.reshape(h, w, c)
+
+
 def save_image_raw(fn, x):
     try:
         try:
@@ -353,6 +404,8 @@ def load_image_raw(fn):
         if os.path.splitext(fn)[1].lower() == '.hdr':          # without an image library: the Radiance reader the checkpoints already use
             from d3h.checkpoint import read_hdr
             return read_hdr(fn)
+        if os.path.splitext(fn)[1].lower() == '.png':
+            return _png_read(fn)
         raise
     return imageio.imread(fn)
 

@@ -1147,9 +1147,99 @@ def gen_data_edges():
     np.savez_compressed(os.path.join(GOLD, 'data_edges.npz'), **npy(out))
 
 
+def _savez_reproducible(path, arrays):
+    """np.savez_compressed with the archive's time stamps pinned (numpy writes the wall clock into every entry), so that a second run gives the same bytes"""
+    import io, zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[k]), allow_pickle=False)
+            info = zipfile.ZipInfo(k + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(info, buf.getvalue())
+
+
+def gen_texture2d():
+    """reference render/texture.py (:20-182) and render/material.py (:72-93) on the CPU: texture2d_mip forward / backward, Texture2D.sample in
+    its three forms (one image with on-the-fly mips, a custom mip chain, a constant), create_trainable(auto_mipmaps=False), clamp_, and the
+    text save_mtl writes.  `nvdiffrast.torch` is the BUILD's shim on the host emulation of its kernels (the reference's texture2d_mip backward
+    and Texture2D.sample are calls of dr.texture), everything under `render` is the reference's."""
+    import tempfile
+    refharness.install()
+    build = os.path.join(ROOT, 'd3human-code_amd')
+    sys.path.append(build)                                     # AFTER the reference: only `d3h` and the `nvdiffrast` shim resolve to the build
+    for n in ('nvdiffrast', 'nvdiffrast.torch'):
+        sys.modules.pop(n, None)
+    from d3h import _lib as L
+    emul = os.path.join(ROOT, 'tests', 'emul', 'libd3h_emul.so')
+    if not os.path.exists(emul):
+        import subprocess
+        subprocess.check_call([os.path.join(ROOT, 'tests', 'emul', 'build_emul.sh')])
+    L._use_emulator_for_tests(emul)
+    _linspace = torch.linspace                                 # texture2d_mip.backward runs inside the autograd engine, where the device-rewriting
+    torch.linspace = lambda *a, device=None, **k: _linspace(*a, **k)      # mode of refharness is not active: its two device="cuda" grids, on the CPU
+    sys.modules['imageio'].imwrite = lambda *a, **k: None       # save_mtl writes its PNGs through imageio: only the .mtl text is recorded
+    out = {}
+    with refharness.ref_ctx():
+        from render import texture as rtex, material as rmat
+        assert rtex.__file__.startswith(refharness.REF) and rmat.__file__.startswith(refharness.REF) and rtex.dr.__file__.startswith(build)
+        G = lambda seed: torch.Generator().manual_seed(seed)
+        # ---- texture2d_mip ----
+        for i, shp in enumerate(((1, 2, 2, 1), (2, 6, 4, 3), (1, 8, 8, 4), (1, 4, 4, 6))):
+            x = (torch.rand(*shp, generator=G(10 + i)) * 2 - 1).requires_grad_(True)
+            y = rtex.texture2d_mip.apply(x)
+            dout = torch.rand(*y.shape, generator=G(20 + i)) * 2 - 1
+            out.update({f'mip{i}.x': x.detach(), f'mip{i}.out': y.detach(), f'mip{i}.dout': dout})
+            if shp[0] == 1:          # the reference's backward looks dout up with ONE uv grid ([1,2h,2w,2]): it has no form for a batch of images
+                y.backward(dout)
+                out[f'mip{i}.grad'] = x.grad
+        # ---- Texture2D.sample ----
+        uv = torch.rand(1, 4, 5, 2, generator=G(30)) * 1.2 - 0.1
+        # footprints from a 30th of a texel to several textures wide, so that every level of a 4-level chain is read
+        uv_da = (torch.rand(1, 4, 5, 4, generator=G(31)) * 2 - 1) * (2.0 ** torch.linspace(-8, 1, 20)).reshape(1, 4, 5, 1)
+        wgt = torch.rand(1, 4, 5, 3, generator=G(32)) * 2 - 1
+        out.update({'sample.uv': uv, 'sample.uv_da': uv_da, 'sample.wgt': wgt})
+        img = torch.rand(1, 8, 8, 3, generator=G(33)).requires_grad_(True)
+        o = rtex.Texture2D(img).sample(uv, uv_da)
+        (o * wgt).sum().backward()
+        out.update({'auto.tex': img.detach(), 'auto.out': o.detach(), 'auto.grad': img.grad})
+        chain = rtex.create_trainable(torch.rand(8, 4, 3, generator=G(34)), auto_mipmaps=False)
+        assert isinstance(chain.data, list) and len(chain.data) == 4
+        o = chain.sample(uv, uv_da)
+        (o * wgt).sum().backward()
+        for k, lv in enumerate(chain.data):
+            out[f'list.level{k}'], out[f'list.grad{k}'] = lv.detach(), lv.grad
+        out['list.out'] = o.detach()
+        const = torch.tensor([0.2, 0.5, 0.7])
+        out.update({'const.value': const, 'const.out': rtex.Texture2D(const).sample(uv, uv_da).detach()})
+        # ---- create_trainable(auto_mipmaps=False) with a resample, clamp_ ----
+        init = torch.rand(6, 4, 3, generator=G(35))
+        t = rtex.create_trainable(init, res=[8, 8], auto_mipmaps=False, min_max=None)
+        out['trainable.init'] = init
+        for k, lv in enumerate(t.data):
+            assert lv.requires_grad and lv.is_leaf
+            out[f'trainable.level{k}'] = lv.detach()
+        data = torch.rand(1, 4, 4, 3, generator=G(36)) * 3 - 1
+        lo, hi = torch.tensor([0.0, 0.1, -0.5]), torch.tensor([1.0, 0.6, 0.5])
+        c = rtex.Texture2D(data.clone(), min_max=[lo, hi])
+        c.clamp_()
+        out.update({'clamp.data': data, 'clamp.lo': lo, 'clamp.hi': hi, 'clamp.out': c.data})
+        # ---- save_mtl ----
+        with tempfile.TemporaryDirectory() as d:
+            mat = {'bsdf': 'pbr', 'kd': rtex.Texture2D(torch.rand(1, 4, 4, 3, generator=G(37))), 'ks': rtex.Texture2D(torch.rand(1, 4, 4, 3, generator=G(38))),
+                   'normal': rtex.Texture2D(torch.rand(1, 4, 4, 3, generator=G(39)))}
+            rmat.save_mtl(os.path.join(d, 'mesh.mtl'), mat)
+            out['mtl.text'] = np.array(open(os.path.join(d, 'mesh.mtl')).read())
+            rmat.save_mtl(os.path.join(d, 'none.mtl'), None)
+            out['mtl.text_none'] = np.array(open(os.path.join(d, 'none.mtl')).read())
+    print('texture2d:', len(out), 'entries; mtl text', repr(str(out['mtl.text'])))
+    _savez_reproducible(os.path.join(GOLD, 'texture2d.npz'), npy(out))
+
+
 # dependency order: imgops / render read mtets_gshell_n8.npz, tick_split / tick_seq read tick_init.npz, tick_seq reads seq.npz (from GOLD)
 ALL = {'sdf_mlp': gen_sdf_mlp, 'mtets': gen_mtets, 'lbs': gen_lbs, 'imgops': gen_imgops, 'render': gen_render, 'seq': gen_seq, 'lpips': gen_lpips,
-       'data_edges': gen_data_edges, 'tick_init': gen_tick_init, 'tick_split': gen_tick_split, 'tick_seq': gen_tick_seq}
+       'data_edges': gen_data_edges, 'tick_init': gen_tick_init, 'tick_split': gen_tick_split, 'tick_seq': gen_tick_seq,
+       'texture2d': gen_texture2d}
 
 if __name__ == '__main__':
     names = sys.argv[1:] or list(ALL)

@@ -10,8 +10,8 @@ body, the total of :1087, both optimisers) and `train.optimize_mesh_seq` (train.
 validate_all_mesh + the .ply / .npz outputs at the end).  optimize_mesh_seq loops a hard-coded 1000 (or 300) times; the harness
 shortens that by giving the train MODULE a `range` that yields the first `--iters` indices and the last one (the function, hence the
 file, is untouched; every statement of the loop body, the final validation and the delta / visible-triangle dump run).  All with
-`geometry`, `render`, `deform`, `nvdiffrast`, `tinycudann`, `kaolin`, `pytorch3d`, `ssim_loss`, `lap_loss` resolving to this build and
-`dataset` resolving to this build and everything else (`render.{material,texture,light}`, `denoiser`, `script`) to the reference's files.  Inputs the
+`geometry`, `render` (`render.material` and `render.texture` included), `deform`, `nvdiffrast`, `tinycudann`, `kaolin`, `pytorch3d`, `ssim_loss`,
+`lap_loss` and `dataset` resolving to this build, and only `train` itself and `script` to the reference's files.  Inputs the
 repository does not ship are synthetic: the sequence (the build's Dataset_split over an in-memory frame), the SMPL-X model (d3h.synth), the tet grid, the merged body + garment mesh of the seq stage (an ellipsoid and an open tube, labels
 prepared as train.py:1885-1911 does).  Third-party modules that train.py imports at the top but these stages never call
 (xatlas, cv2, openmesh, tensorboardX, imageio, open3d, pymeshlab, pysdf, trimesh, torchvision) are stubbed when absent.
@@ -85,12 +85,13 @@ def main():
     dev = 'cpu' if a.emulator else 'cuda'
 
     import train                                                     # the reference's train.py
-    import geometry.hmsdf, render.render, render.util, render.material, dataset.dataset_split   # noqa: F401,E401
+    import geometry.hmsdf, render.render, render.util, render.material, render.texture, dataset.dataset_split   # noqa: F401,E401
     where = {m: os.path.relpath(sys.modules[m].__file__, ROOT) if sys.modules[m].__file__.startswith(ROOT) else sys.modules[m].__file__
-             for m in ('train', 'geometry.hmsdf', 'render.render', 'render.util', 'render.material', 'dataset.dataset_split', 'nvdiffrast.torch')}
+             for m in ('train', 'geometry.hmsdf', 'render.render', 'render.util', 'render.material', 'render.texture', 'dataset.dataset_split', 'nvdiffrast.torch')}
     print("resolved:", where, flush=True)
     assert where['geometry.hmsdf'].startswith('d3human-code_amd') and where['render.render'].startswith('d3human-code_amd')
-    assert 'd3human-code_amd' not in where['train'] and 'd3human-code_amd' not in where['render.material']
+    assert 'd3human-code_amd' not in where['train']
+    assert where['render.material'].startswith('d3human-code_amd') and where['render.texture'].startswith('d3human-code_amd')
     assert where['dataset.dataset_split'].startswith('d3human-code_amd')              # train.py:25 `from dataset.dataset_split import Dataset_split`
 
     from d3h import synth
