@@ -187,8 +187,10 @@ def _edge_map(tri):
     return m
 
 
-def antialias(color, rast, pos, tri):
-    """color [B,H,W,C], rast [B,H,W,4], pos [B or 1,V,4] (torch, differentiable in color and pos)"""
+def antialias(color, rast, pos, tri, return_pairs=False):
+    """color [B,H,W,C], rast [B,H,W,4], pos [B or 1,V,4] (torch, differentiable in color and pos).
+    return_pairs: -> (out, (b, pi, po, d)), per blended pair the frame, the flat indices of the inner and the outer pixel and the (detached)
+    crossing position d in the dtype of `pos` (tests/raster64_cases.py: which pairs sit next to a kink of |d - 0.5|)"""
     B, H, W, C = color.shape
     emap = _edge_map(tri)
     rn = rast.detach().numpy()
@@ -252,7 +254,8 @@ def antialias(color, rast, pos, tri):
                         break
     out = color.reshape(B, H * W, C).clone()
     if not items:
-        return out.reshape(B, H, W, C)
+        e = torch.zeros(0, dtype=torch.long)
+        return (out.reshape(B, H, W, C), (e, e, e, torch.zeros(0, dtype=pos.dtype))) if return_pairs else out.reshape(B, H, W, C)
     it = np.array([[i[0], i[1], i[2], i[3], i[4], i[5]] for i in items], np.int64)
     cen = torch.tensor([[i[6], i[7], i[8], i[9]] for i in items], dtype=torch.float32)
     bb, pi, po, dirx, va, vb = [torch.from_numpy(it[:, k]) for k in range(6)]
@@ -275,4 +278,4 @@ def antialias(color, rast, pos, tri):
     cin = color.reshape(B, H * W, C)
     delta = alpha.abs()[:, None] * (cin[bb, src] - cin[bb, dst])
     out = out.index_put((bb, dst), delta, accumulate=True)
-    return out.reshape(B, H, W, C)
+    return (out.reshape(B, H, W, C), (bb, pi, po, d.detach())) if return_pairs else out.reshape(B, H, W, C)
