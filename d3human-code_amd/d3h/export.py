@@ -4,10 +4,14 @@ render/obj.py:write_obj writes as mesh.obj + mesh.mtl + three PNGs (the referenc
 The chart is the closed-form triangle-pair atlas of d3h.uvatlas, the bake evaluates the material once per texel at the position of the
 owning triangle's affine map (gutter texels included, so nothing is dilated), and a level-0 bilinear lookup anywhere on the surface reads
 texels of its own triangle only.  The maps are for level-0 bilinear use (mip levels above 0 mix triangles); (s - 4)^2 / s^2 of the texels of
-a cell carry surface.  `render.render.render_uv` is the rasterising route of the reference and stays as a cross-check."""
+a cell carry surface: the exported material says so with 'filter_mode': 'linear', which render.render.render_mesh honours (its default,
+the mip-mapped Texture2D.sample, is off by up to 0.56 on values within +-0.6 on such a bake; level-0 bilinear stays within 3.9e-7).
+`load_textured_mesh` reads the files write_obj wrote back as a renderable mesh.  `render.render.render_uv` is the rasterising route of the reference and stays as a cross-check."""
+import os
+
 import torch
 
-from render import mesh as _mesh, texture as _texture
+from render import material as _material, mesh as _mesh, obj as _obj, texture as _texture
 from . import uvatlas as _U
 
 
@@ -15,7 +19,7 @@ from . import uvatlas as _U
 def textured_mesh(mesh, material, texture_res, kd_min, kd_max, ks_min, ks_max, nrm_min, nrm_max):
     """mesh: render.mesh.Mesh (v_pos [V,3], or [B,V,3] posed frames of which the first is baked); material: dict with 'kd_ks', an MLPTexture3D
     of 6 channels; texture_res: (H, W) or one int.  -> Mesh(v_tex, t_tex_idx, base=mesh) whose material is `material` without 'kd_ks' and with
-    'kd', 'ks', 'normal' as trainable Texture2D ([1,H,W,3] each) clamped to the given ranges; texels no triangle owns hold the mean of the owned ones."""
+    'kd', 'ks', 'normal' as trainable Texture2D ([1,H,W,3] each) clamped to the given ranges and 'filter_mode': 'linear' (module docstring); texels no triangle owns hold the mean of the owned ones."""
     v_pos = mesh.v_pos[0] if mesh.v_pos.dim() == 3 else mesh.v_pos
     atlas = _U.make_atlas(v_pos, mesh.t_pos_idx, texture_res)
     pos, owned, _, _ = _U.bake_positions(atlas, v_pos, mesh.t_pos_idx)
@@ -29,7 +33,40 @@ def textured_mesh(mesh, material, texture_res, kd_min, kd_max, ks_min, ks_max, n
     leaf = lambda t: t.clone().detach().contiguous().requires_grad_(True)
     out = _mesh.Mesh(v_tex=atlas.uvs, t_tex_idx=atlas.t_tex_idx, base=mesh)
     out.material = {k: v for k, v in material.items() if k != 'kd_ks'}
+    out.material['filter_mode'] = 'linear'
     out.material.update({'kd': _texture.Texture2D(leaf(tex[..., 0:3]), min_max=rng(kd_min, kd_max)),
                          'ks': _texture.Texture2D(leaf(tex[..., 3:6]), min_max=rng(ks_min, ks_max)),
                          'normal': _texture.Texture2D(leaf(normal), min_max=rng(nrm_min, nrm_max))})
     return out
+
+
+def load_textured_mesh(obj_path, filter_mode='linear', clear_ks=False, device=None):
+    """mesh.obj + the first material of the .mtl next to it (the `mtllib` line's file, mesh.mtl when there is none) -> a Mesh render_mesh can draw:
+    positions, uvs and faces of render.obj.load_obj, the file's normals or auto_normals when it has no `vn`, tangents from compute_tangents, and
+    the material of render.material.load_mtl with 'filter_mode' set (what the maps were baked for: module docstring).  Everything on `device`
+    (None: the GPU when there is one)."""
+    m = _obj.load_obj(obj_path, device=device)
+    if m.v_tex is None or m.t_tex_idx is None:
+        raise ValueError(f'load_textured_mesh: {obj_path} has no texture coordinates')
+    mtl = 'mesh.mtl'
+    with open(obj_path) as fh:
+        for line in fh:
+            p = line.split()
+            if len(p) > 1 and p[0].lower() == 'mtllib':
+                mtl = p[1]
+                break
+    mats = _material.load_mtl(os.path.join(os.path.dirname(obj_path), mtl), clear_ks=clear_ks)
+    if not mats:
+        raise ValueError(f'load_textured_mesh: {mtl} defines no material')
+    mat = dict(mats[0])
+    dev = m.v_pos.device
+    for k, v in mat.items():
+        if isinstance(v, _texture.Texture2D):
+            v.data = [l.to(dev) for l in v.data] if isinstance(v.data, list) else v.data.to(dev)
+        elif torch.is_tensor(v):
+            mat[k] = v.to(dev)
+    mat['filter_mode'] = filter_mode
+    m.material = mat
+    if m.v_nrm is None:
+        m = _mesh.auto_normals(m)
+    return _mesh.compute_tangents(m)

@@ -2,11 +2,17 @@
 
 Difference kept deliberately small but important for MI355X: the reference's constructor sorts + uniques all 3F edges on EVERY
 construction (mesh.py:162,240-250; ~8 radix sorts per getMesh_* that init/split never read).  Here `edges` is computed on first
-access with the same definition.  `t_pos_idx32` is the int32 view the HIP kernels consume."""
+access with the same definition.  `t_pos_idx32` is the int32 view the HIP kernels consume.
+
+`compute_tangents` (mesh.py:452-495), `aabb`, `unit_size`, `center_by_reference` and `load_mesh` (mesh.py:285-295,364-380) are the reference's, on
+the tensors' own device."""
+import os
+
 import torch
 
 from d3h import imgops as _I
 from d3h import meshops as _M
+from . import util
 
 find_edges = _M.find_edges                          # mesh.py:85-103
 find_connected_faces = _M.find_connected_faces      # mesh.py:106-134 (vectorised; same pairs, same order)
@@ -146,3 +152,64 @@ def auto_normals(imesh, lazy=False):
         return m
     v_nrm = _I.auto_normals(v, f32)             # one launch for the whole batch of posed frames
     return Mesh(v_nrm=v_nrm, t_nrm_idx=imesh.t_pos_idx, base=imesh)
+
+
+def compute_tangents(imesh, v_tng=None):
+    """mesh.py:452-495, the tangent space of the uv chart (mikktspace conventions): per triangle (pe1 dv2 - pe2 dv1) / (du1 dv2 - dv1 du2) from
+    its position and uv edges, the denominator kept at least 1e-6 away from zero with its sign (zero counts as negative), averaged over the
+    triangles at each vertex named by t_nrm_idx, normalised, made perpendicular to v_nrm (Gram-Schmidt) and normalised again.  `v_tng` given: only
+    the last two steps, on it.  v_pos / v_nrm may be [V,3] or [B,V,3] (posed frames sharing faces and uvs); differentiable in both.  Not on the
+    per-pixel path: library scatter ops.  A normal no triangle names gets 0 / 0, as in the reference.
+    -> Mesh(v_tng=..., t_tng_idx=imesh.t_nrm_idx, base=imesh)"""
+    v_nrm = imesh.v_nrm
+    if v_tng is None:
+        v_pos = imesh.v_pos
+        if v_pos.dim() != v_nrm.dim():
+            raise ValueError(f'compute_tangents: v_pos {tuple(v_pos.shape)} and v_nrm {tuple(v_nrm.shape)} must both be [V,3] or both [B,V,3]')
+        pos = [v_pos[..., imesh.t_pos_idx[:, i], :] for i in range(3)]
+        tex = [imesh.v_tex[imesh.t_tex_idx[:, i]] for i in range(3)]
+        uve1, uve2 = tex[1] - tex[0], tex[2] - tex[0]
+        pe1, pe2 = pos[1] - pos[0], pos[2] - pos[0]
+        nom = pe1 * uve2[..., 1:2] - pe2 * uve1[..., 1:2]
+        denom = uve1[..., 0:1] * uve2[..., 1:2] - uve1[..., 1:2] * uve2[..., 0:1]
+        tang = nom / torch.where(denom > 0.0, torch.clamp(denom, min=1e-6), torch.clamp(denom, max=-1e-6))
+        tangents, tansum = torch.zeros_like(v_nrm), torch.zeros_like(v_nrm)
+        ones = torch.ones_like(tang)
+        for i in range(3):
+            tangents = tangents.index_add(-2, imesh.t_nrm_idx[:, i], tang)
+            tansum = tansum.index_add(-2, imesh.t_nrm_idx[:, i], ones)
+        v_tng = tangents / tansum
+    v_tng = util.safe_normalize(v_tng)
+    v_tng = util.safe_normalize(v_tng - util.dot(v_tng, v_nrm) * v_nrm)
+    if torch.is_anomaly_enabled():
+        assert torch.all(torch.isfinite(v_tng))
+    return Mesh(v_tng=v_tng, t_tng_idx=imesh.t_nrm_idx, base=imesh)
+
+
+def aabb(mesh):
+    """mesh.py:294-295"""
+    return torch.min(mesh.v_pos, dim=0).values, torch.max(mesh.v_pos, dim=0).values
+
+
+def unit_size(mesh):
+    """mesh.py:364-371: centred on the origin, the longest side of the bounding box scaled to 2"""
+    with torch.no_grad():
+        vmin, vmax = aabb(mesh)
+        scale = 2 / torch.max(vmax - vmin).item()
+        return Mesh((mesh.v_pos - (vmax + vmin) / 2) * scale, base=mesh)
+
+
+def center_by_reference(base_mesh, ref_aabb, scale):
+    """mesh.py:376-380: centred on the reference box, its longest side scaled to `scale`"""
+    center = (ref_aabb[0] + ref_aabb[1]).to(base_mesh.v_pos.device) * 0.5
+    scale = scale / torch.max(ref_aabb[1] - ref_aabb[0]).item()
+    return Mesh((base_mesh.v_pos - center[None, ...]) * scale, base=base_mesh)
+
+
+def load_mesh(filename, mtl_override=None, mtl_default=None, mtl_type_override=None):
+    """mesh.py:285-289"""
+    from . import obj
+    ext = os.path.splitext(filename)[1]
+    if ext == '.obj':
+        return obj.load_obj(filename, clear_ks=True, mtl_override=mtl_override, mtl_default=mtl_default, mtl_type_override=mtl_type_override)
+    assert False, 'Invalid mesh file extension'

@@ -12,6 +12,18 @@ FLAGS.lit_shading (an extension, off by default) makes the branch of render.py:1
 PBR / diffuse / white combine -- `shade_lit`.  Without the flag nothing of it is touched: `lgt`, `optix_ctx`, `bsdf`, `denoiser` and
 `shadow_scale` are accepted and ignored, as before.
 
+2-D materials (the exported mesh of d3h.export.textured_mesh, or any material with 'kd' / 'ks' / 'normal' as Texture2D and no 'kd_ks'): the texel
+coordinate is interpolated from mesh.v_tex by mesh.t_tex_idx and the maps are read with material['filter_mode'] (default 'linear-mipmap-linear', the
+reference's Texture2D.sample; 'linear' / 'nearest' are level-0 lookups, boundary 'wrap', what the triangle-pair atlas is baked for).  Normals and
+tangents go by t_nrm_idx / t_tng_idx.  With use_uv, finetune_normal, a 'normal' map (and no true 'no_perturbed_nrm') and mesh.v_tng the normal map
+perturbs the shading normal in the interpolated tangent frame and 'perturbed_nrm' / 'perturbed_nrm_grad' (render.py:106-109,202-204) join the
+outputs.  'kd_grad' / 'ks_grad' are SCREEN-SPACE there, built like normal_grad: |tap(kd, jitter) - kd| * grad_weight (ks times (0, 1, 1)), tap the
+bilinear / clamp lookup of the image at the jittered pixel grid -- the reference has no 2-D rule (its jitter is a 3-D position offset into the MLP),
+and a jitter in uv space would leave the triangle's cell of the atlas.  The lookups are one fused pass (d3h.texmat) when the mode is 'linear', the
+raster and v_tex need no gradient and shading runs at the visibility resolution; else interpolate + texture, which gives the same values.
+D3H_TEXMAT_FUSED=0 / 1 forces the composed / fused route where both apply (default: profiles/texmat_probe.md).  A 4-channel kd (transparency) is not
+built.
+
 `mesh.v_pos` may be [P,3] (the reference) or [B,P,3] (one posed mesh per frame of the batch: the build's N-frame extension,
 SURVEY F5).  spp > 1 is not part of the hot path (FLAGS.spp = 1) and raises.
 """
@@ -26,11 +38,15 @@ from . import renderutils as ru
 from . import optixutils as ou
 from d3h import imgops as _I
 from d3h import raster as _R
+from d3h import texmat as _TM
+from .texture import Texture2D as _Texture2D
 
 ALL_BUFFERS = ('shaded', 'z_grad', 'normal', 'geometric_normal', 'kd', 'ks', 'kd_grad', 'ks_grad', 'normal_grad', 'depth', 'invdepth')
 LIT_BUFFERS = ('diffuse_light', 'specular_light')          # render.py:197-200: present only when the lit branch ran
 LIT_BSDFS = ('pbr', 'diffuse', 'white')
 BSDFS = ('kd', 'ks', 'normal', 'tangent') + LIT_BSDFS
+PERTURBED_BUFFERS = ('perturbed_nrm', 'perturbed_nrm_grad')   # render.py:202-204: present only when a normal map perturbs the shading normal
+TEXMAT_FUSED_DEFAULT = True                                # profiles/texmat_probe.md
 rnd_seed = 0                                               # render.py:128-132: the sampler's seed, one step per lit shade
 
 
@@ -147,27 +163,61 @@ def _frame_contexts(optix_ctx, B):
     return ctxs
 
 
+def is_texture_material(material):
+    """a 2-D material: no 'kd_ks', and 'kd' and 'ks' as Texture2D"""
+    return isinstance(material, dict) and ('kd_ks' not in material) and isinstance(material.get('kd'), _Texture2D) and isinstance(material.get('ks'), _Texture2D)
+
+
+def _texmat_fused():
+    env = os.environ.get('D3H_TEXMAT_FUSED')
+    return TEXMAT_FUSED_DEFAULT if env is None else env != '0'
+
+
+def _material_lookups(mesh, rast, db, names, same_res, mask):
+    """{name: [B,H,W,C]} of the material's maps `names` at the pixels' texel coordinates (module docstring), zero at uncovered pixels on either
+    route (the composed lookups read texel (0, 0) there: masked, so that the screen-space taps next to the silhouette see the same image)"""
+    material = mesh.material
+    mode = material.get('filter_mode', 'linear-mipmap-linear')
+    mip = mode.startswith('linear-mipmap')
+    texs = [material[k] for k in names]
+    if not names:
+        return {}
+    level0 = [t.getMips()[0] for t in texs]
+    fused_ok = (mode == 'linear' and same_res and not mip and all(l.shape[0] == 1 and l.shape[-1] <= _TM.MAX_CHANNELS for l in level0)
+                and not (torch.is_grad_enabled() and (rast.requires_grad or mesh.v_tex.requires_grad)))
+    if fused_ok and _texmat_fused():
+        return dict(zip(names, _TM.lookup(rast.detach(), mesh.v_tex.detach(), mesh.t_tex_idx.int(), level0, boundary='wrap')))
+    if mip:
+        texc, texc_deriv = interpolate(mesh.v_tex[None, ...], rast, mesh.t_tex_idx.int(), rast_db=db)
+        return {k: t.sample(texc, texc_deriv, filter_mode=mode) * mask for k, t in zip(names, texs)}
+    texc, _ = interpolate(mesh.v_tex[None, ...], rast, mesh.t_tex_idx.int())
+    return {k: dr.texture(l, texc, filter_mode=mode, boundary_mode='wrap') * mask for k, l in zip(names, level0)}
+
+
 def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, gb_normal, gb_tangent, view_pos, material, want,
-          finetune_normal=True, mask=None, rng_draws=None, live=None, skip_uncovered=True, lit=None):
+          finetune_normal=True, mask=None, rng_draws=None, live=None, skip_uncovered=True, lit=None, tex2d=None):
     """render.py:42-205 with perturbed_nrm None.  `lit` None: the branch the reference's hard-wired bsdf = 'kd' leaves live, exactly; else
     (bsdf, lgt, contexts, denoiser, shadow_scale) of FLAGS.lit_shading: 'shaded' follows the bsdf (render.py:121-176).  `aux` = (z_grad values, depth, invdepth) from
     the fused forward-only pass (d3h.raster.aux_buffers; entries None where not produced); `live`: the buffers that need a gradient
-    (None = all) -- the producers of the others run under torch.no_grad()."""
+    (None = all) -- the producers of the others run under torch.no_grad().
+    `tex2d` (a 2-D material, module docstring): {'lookup': names -> {name: image}, 'perturb': bool}; then 'kd_ks' is not read, `pos_noise` neither drawn
+    nor read, and kd_grad / ks_grad are the screen-space rule."""
     B, H, W = rast.shape[:3]
     dev = rast.device
     grad_on = torch.is_grad_enabled()
     on = lambda *ks: torch.set_grad_enabled(grad_on and (live is None or any(k in live for k in ks)))
     if mask is None:
         mask = (rast[..., -1:] > 0).float()                                       # render.py:66
-    need_jitter = bool(want & {'normal_grad', 'kd_grad', 'ks_grad'})
+    need_jitter = bool(want & {'normal_grad', 'kd_grad', 'ks_grad', 'perturbed_nrm_grad'})
     # RNG call order follows the reference (offset, then the position jitter) so a seeded CPU run reproduces it
     if rng_draws is not None:            # pre-drawn jitter (tests: the same draws on every device)
-        offset, pos_noise = rng_draws['offset'].to(dev), rng_draws['pos_noise'].to(dev)
+        offset, pos_noise = rng_draws['offset'].to(dev), (rng_draws['pos_noise'].to(dev) if tex2d is None else None)
     else:
         offset = torch.normal(mean=0, std=0.005, size=(B, H, W, 2), device=dev) if need_jitter else None
-        pos_noise = torch.normal(mean=0, std=0.01, size=gb_pos_original.shape, device=dev) if need_jitter else None
+        pos_noise = torch.normal(mean=0, std=0.01, size=gb_pos_original.shape, device=dev) if need_jitter and tex2d is None else None
 
-    kd_ks = material['kd_ks']
+    kd_ks = material['kd_ks'] if tex2d is None else None
+    perturbed_nrm = None
     # the texture MLP skips uncovered pixels (their value never reaches an output: alpha = 0) -- except under supersampling, where a
     # covered sub-pixel can inherit the value of an uncovered shading pixel (render.py:241-245,334-336): then every pixel is evaluated
     tex_mask = mask if skip_uncovered else None
@@ -178,11 +228,37 @@ def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, g
     # gradient (a tick of the split / seq stage) or none does; in the mixed case (the 'all' mode of a tick) the dead ones stay separate
     # torch ops under no_grad so that the backward does not pay for them
     smooth = want & {'kd_grad', 'ks_grad', 'normal_grad'}
-    fused = ({'kd_grad', 'ks_grad'} <= want) and (not grad_on or all(is_live(k) for k in smooth | (want & {'shaded', 'kd'})))
+    fused = tex2d is None and ({'kd_grad', 'ks_grad'} <= want) and (not grad_on or all(is_live(k) for k in smooth | (want & {'shaded', 'kd'})))
     # ... and when NONE of the smoothness buffers is live (tick_init in its 'all' mode) they come out of the same pass under no_grad, kd staying
     # the plain slice that carries the gradient
-    fused_dead = (not fused) and ({'kd_grad', 'ks_grad'} <= want) and grad_on and not any(is_live(k) for k in smooth)
-    if want & set(tex_users):
+    fused_dead = tex2d is None and (not fused) and ({'kd_grad', 'ks_grad'} <= want) and grad_on and not any(is_live(k) for k in smooth)
+    if tex2d is not None:
+        # ---- 2-D material: the maps at the texel coordinate; the smoothness terms in screen space (module docstring)
+        names = [k for k, users in (('kd', {'shaded', 'kd', 'kd_grad'}), ('ks', {'ks', 'ks_grad'})) if want & users]
+        nrm_users = {'normal', 'perturbed_nrm', 'perturbed_nrm_grad'}
+        if tex2d['perturb'] and want & nrm_users:
+            names.append('normal')
+        with on(*tex_users, *nrm_users):
+            vals = tex2d['lookup'](names)
+        kd, ks, perturbed_nrm = vals.get('kd'), vals.get('ks'), vals.get('normal')
+        ks = ks[..., 0:3] if ks is not None else None
+        if want & {'kd_grad', 'ks_grad', 'perturbed_nrm_grad'}:
+            jitter = (util.pixel_grid(W, H, device=dev)[None, ...] + offset).contiguous()
+            tap = lambda img: dr.texture(img.contiguous(), jitter, filter_mode='linear', boundary_mode='clamp')
+            grad_weight = mask * tap(mask)                                     # render.py:72-73
+            if 'kd_grad' in want:
+                with on('kd_grad'):
+                    out['kd_grad'] = torch.abs(tap(kd) - kd) * grad_weight
+            if 'ks_grad' in want:
+                with on('ks_grad'):
+                    out['ks_grad'] = torch.abs(tap(ks) - ks) * grad_weight * _const((0.0, 1.0, 1.0), dev)
+            if 'perturbed_nrm_grad' in want and perturbed_nrm is not None:
+                with on('perturbed_nrm_grad'):                                  # render.py:106-109
+                    both = util.safe_normalize(util.safe_normalize(tap(perturbed_nrm)) + util.safe_normalize(perturbed_nrm))
+                    out['perturbed_nrm_grad'] = (1.0 - both[..., 2:3]).repeat(1, 1, 1, 3) * grad_weight
+        if 'perturbed_nrm' in want and perturbed_nrm is not None:
+            out['perturbed_nrm'] = perturbed_nrm
+    elif want & set(tex_users):
         with on(*tex_users):
             all_tex = kd_ks.sample(gb_pos_original, idx, mask=tex_mask)
         kd = _I.first_channels(all_tex, 3)           # (the channels the shaded colour carries: a one-pass gradient instead of the slice node's fill + copy)
@@ -212,7 +288,7 @@ def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, g
             _, out['kd_grad'], out['ks_grad'], ng = _I.material_grads(all_tex, all_tex_jitter, *nrm_in, want_kd=False)
             if ng is not None:
                 out['normal_grad'] = ng
-    elif want & {'kd_grad', 'ks_grad'}:
+    elif tex2d is None and want & {'kd_grad', 'ks_grad'}:
         with on('kd_grad', 'ks_grad'):
             all_tex_jitter = kd_ks.sample(gb_pos_original + pos_noise, idx, mask=tex_mask)
             out['kd_grad'] = torch.abs(all_tex_jitter[..., 0:3] - kd)
@@ -226,7 +302,7 @@ def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, g
             out['normal_grad'] = torch.abs(nrm_jitter - gb_normal) * (mask * mask_tap)
     if 'normal' in want:
         with on('normal'):
-            out['normal'] = ru.prepare_shading_normal(gb_pos, view_pos, None, gb_normal, gb_tangent, gb_geometric_normal, two_sided_shading=True,
+            out['normal'] = ru.prepare_shading_normal(gb_pos, view_pos, perturbed_nrm, gb_normal, gb_tangent, gb_geometric_normal, two_sided_shading=True,
                                                       opengl=True)
     if 'shaded' in want and lit is not None:
         bsdf, lgt, ctxs, denoiser, shadow_scale = lit
@@ -243,7 +319,7 @@ def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, g
                 out['shaded'] = kd if bsdf == 'kd' else ks
     elif 'shaded' in want:
         out['shaded'] = kd                                         # bsdf = 'kd' (render.py:120,169-170)
-        if not fused:
+        if not fused and tex2d is None:
             out['_shaded_of'] = all_tex                            # kd IS all_tex[..., :3]: the fused composite takes the wide tensor (compose)
     if 'kd' in want:
         out['kd'] = kd
@@ -287,6 +363,20 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     if extra_dict is not None and extra_dict.get('msdf') is not None and (buffers is None or 'msdf_image' in buffers):
         want.add('msdf_image')
     grad_on = torch.is_grad_enabled()
+    # ---- a 2-D material (module docstring): what it needs of the mesh, and whether its normal map perturbs the shading normal
+    tex2d = is_texture_material(mesh.material)
+    perturb = False
+    if tex2d:
+        if mesh.v_tex is None or mesh.t_tex_idx is None:
+            raise ValueError("render_mesh: a material with 'kd' / 'ks' texture maps needs mesh.v_tex and mesh.t_tex_idx")
+        if mesh.material['kd'].getChannels() == 4:
+            raise NotImplementedError('render_mesh: a 4-channel kd (transparency, FLAGS.transparency of the reference) is not built')
+        perturb = bool(use_uv and finetune_normal and isinstance(mesh.material.get('normal'), _Texture2D)
+                       and not mesh.material.get('no_perturbed_nrm', False) and mesh.v_tng is not None)
+        if perturb and buffers is None:
+            want |= set(PERTURBED_BUFFERS)
+    if not perturb:
+        want -= set(PERTURBED_BUFFERS)
     live = None if (_grad_buffers is None or not grad_on) else (want & set(_grad_buffers))
     # ---- FLAGS.lit_shading: the colour follows the bsdf (render.py:117-176).  `want` grows by what the lit colour is made of, so that a caller that
     # reads only 'shaded' still gets positions, shading normal, kd / ks and the denoiser's (z, |dz|); `want_out` / `live_out` stay what was asked for
@@ -319,7 +409,8 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     need_aux = 'z_grad' in want or no_grad_of('depth') or no_grad_of('invdepth')
     # grad_db=False: db feeds the no-grad z-gradient pass only, so its (spp > 1) rescale below records no autograd node
     with dr.DepthPeeler(ctx, v_pos_clip, tri, [Hf, Wf], grad_db=False) as peeler:
-        rast_full, db_full = peeler.rasterize_next_layer(want_db='z_grad' in want)
+        mip_uv = tex2d and mesh.material.get('filter_mode', 'linear-mipmap-linear').startswith('linear-mipmap')     # the texel footprint
+        rast_full, db_full = peeler.rasterize_next_layer(want_db='z_grad' in want or mip_uv)
     rast, db = rast_full, db_full
     if spp > 1 and msaa:                          # shade at the framebuffer resolution (render.py:241-245): nearest sample of the raster
         rast = util.scale_img_nhwc(rast_full, [H, W], mag='nearest', min='nearest')
@@ -336,15 +427,20 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     has_msdf = 'msdf_image' in want
     need_pos, need_nrm = bool(want & {'normal', 'depth', 'invdepth'}), bool(want & {'normal', 'normal_grad'})
     srcs = []
+    # (a 2-D material reads no canonical position; its normals go by t_nrm_idx, in a pass of their own when that is another index buffer)
+    own_nrm_idx = tex2d and mesh.t_nrm_idx is not None and mesh.t_nrm_idx is not mesh.t_pos_idx
     if need_pos:
         srcs.append(('pos', v_pos))
-    srcs.append(('orig', _batched(mesh_original.v_pos)))
-    if need_nrm:
+    if not tex2d:
+        srcs.append(('orig', _batched(mesh_original.v_pos)))
+    if need_nrm and not own_nrm_idx:
         srcs.append(('nrm', _batched(mesh.v_nrm)))
     if has_msdf:
         m = extra_dict['msdf']
         assert m.dim() == 1 or (m.dim() == 2 and m.size(1) == 1)
         srcs.append(('msdf', m.reshape(1, -1, 1)))
+    if not srcs:
+        srcs.append(('pos', v_pos))               # (the pass also makes the coverage mask and the face normal)
     nb_attr = max(t.shape[0] for _, t in srcs)
     packed = torch.cat([t.expand(nb_attr, -1, -1) for _, t in srcs], dim=-1) if len(srcs) > 1 else srcs[0][1]
     fn = _I.face_normals(v_pos, tri) if want & {'geometric_normal', 'normal'} else None      # [B,F,3], one launch
@@ -354,10 +450,14 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     groups, gb_geometric_normal, cover = _R.gbuffer(packed, [t.shape[-1] for _, t in srcs], rast, tri, face_attr=fn, want_mask=True,
                                                     raster_pos=v_pos_clip if fold else None)
     gb = {k: g for (k, _), g in zip(srcs, groups)}
-    gb_pos, gb_pos_original, gb_normal, gb_msdf = gb.get('pos'), gb['orig'], gb.get('nrm'), gb.get('msdf')
+    gb_pos, gb_pos_original, gb_normal, gb_msdf = gb.get('pos'), gb.get('orig'), gb.get('nrm'), gb.get('msdf')
+    if need_nrm and own_nrm_idx:
+        gb_normal, _ = interpolate(_batched(mesh.v_nrm), rast, mesh.t_nrm_idx.int())                  # render.py:272
 
     gb_tangent = None
-    if 'normal' in want:
+    if perturb and 'normal' in want:
+        gb_tangent, _ = interpolate(_batched(mesh.v_tng), rast, mesh.t_tng_idx.int())                # render.py:273
+    elif 'normal' in want:
         with torch.no_grad():                                                    # render.py:284-287 (use_uv == False branch)
             noise = torch.randn_like(gb_normal) if _rng_draws is None else _rng_draws['noise'].to(dev)
             noise = noise / noise.norm(dim=-1, keepdim=True)
@@ -373,7 +473,8 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     if lit is not None and lit[0] in LIT_BSDFS:
         lit = (lit[0], lit[1], _frame_contexts(optix_ctx, B), lit[3], lit[4])
     layer = shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, gb_normal, gb_tangent, view_pos, mesh.material,
-                  want, finetune_normal, mask=cover, rng_draws=_rng_draws, live=live, skip_uncovered=(H, W) == (Hf, Wf), lit=lit)
+                  want, finetune_normal, mask=cover, rng_draws=_rng_draws, live=live, skip_uncovered=(H, W) == (Hf, Wf), lit=lit,
+                  tex2d={'lookup': lambda names: _material_lookups(mesh, rast, db, names, (H, W) == (Hf, Wf), cover), 'perturb': perturb} if tex2d else None)
     if lit is not None:
         layer = {k: t for k, t in layer.items() if k in want_out}              # what the lit colour was made of is not an output unless asked for
         want, live = want_out, live_out
@@ -416,7 +517,7 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
             img = dr.antialias(_I.composite(rast_full, sources), rast_full, v_pos_clip, tri)
         return (util.avg_pool_nhwc(img, spp) if spp > 1 else img), widths                              # render.py:449
 
-    all_keys = [k for k in list(ALL_BUFFERS) + ['msdf_image'] + list(LIT_BUFFERS) if k in layer]
+    all_keys = [k for k in list(ALL_BUFFERS) + ['msdf_image'] + list(LIT_BUFFERS) + list(PERTURBED_BUFFERS) if k in layer]
     live_keys = all_keys if live is None else [k for k in all_keys if k in live]
     dead_keys = [k for k in all_keys if k not in live_keys]
     # '_stacked' / '_layout': the channel-concatenated image itself, for consumers that read several buffers in one pass
@@ -424,7 +525,8 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     out_buffers = {'_layout': {}}
     for name, keys, no_grad in (('_stacked', live_keys, False), ('_stacked_nograd', dead_keys, True)):
         # (the composite pass takes 12 sources: the reference's 11 buffers and the msdf image fit; the two light images of the lit branch, last in the
-        # order, may overflow into a pass of their own, outside '_stacked' / '_layout', which no consumer of the layout reads them from)
+        # order, may overflow into a pass of their own, outside '_stacked' / '_layout', which no consumer of the layout reads them from; the same holds for
+        # the two perturbed-normal buffers of a 2-D material, which come after them)
         for first in range(0, len(keys), 12):
             chunk = keys[first:first + 12]
             with torch.set_grad_enabled(grad_on and not no_grad):

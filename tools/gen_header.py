@@ -28,9 +28,10 @@ GROUPS = {
     'gridenc.hip': 'tiny-cuda-nn Encoding beyond the one configuration of texmlp.hip (un-vendored; call site render/mlptexture.py:62-79,98): HashGrid / DenseGrid with any level count, 2-D / 3-D inputs, 1 / 2 / 4 / 8 features per entry, hashed levels, Linear / Smoothstep interpolation; gradients for the table and the positions',
     'fusedmlp.hip': 'tiny-cuda-nn Network (FullyFusedMLP / CutlassMLP; un-vendored) and the _MLP of render/mlptexture.py:18-41,100-103 for every shape texmlp.hip does not build: a bias-free MLP of 1..8 hidden layers of 16 / 32 / 64 / 128 neurons, seven activations, row mask, affine output map, forward and backward in one kernel each',
     'uvatlas.hip': 'textured-mesh export, train.py:198-246 (xatlas_uvmap: xatlas.parametrize, un-vendored, + render/render.py:456-472 render_uv + two util.dilate(.., 7)): a closed-form triangle-pair atlas and a position bake whose level-0 bilinear lookups never leave the triangle; render/texture.py:20-30 (texture2d_mip: 2 x 2 mean, the bilinear x2 upsample of 0.25 dout as its gradient rule)',
+    'texmat.hip': 'the 2-D material lookups of shade(), render/render.py:277 (interpolate of v_tex by t_tex_idx) + render/texture.py:59-67 (Texture2D.sample of kd, ks, normal) at level 0: texel coordinate and up to three bilinear lookups per pixel in one pass, map gradients by fp32 atomics',
     'texmlp.hip': 'render/mlptexture.py:91-107 (MLPTexture3D.sample): tiny-cuda-nn HashGrid encoding (:62-79, un-vendored) + _MLP (:18-41) + sigmoid range map',
 }
-ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'envshade.hip', 'envlight.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'uvatlas.hip', 'optim.hip', 'timing.hip']
+ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'envshade.hip', 'envlight.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'uvatlas.hip', 'texmat.hip', 'optim.hip', 'timing.hip']
 head = '''/* d3h.h -- C ABI of libd3h_hip.so: the MI355X (gfx950) hot path of D3-Human's render-and-fit loop.
  * GENERATED by tools/gen_header.py from the extern "C" definitions in d3human-code_amd/csrc/ -- do not edit by hand.
  *
