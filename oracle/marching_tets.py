@@ -114,11 +114,18 @@ def _edge_weights(s_pair):
     return torch.stack([b / den, a / den], dim=1)
 
 
-def gshell_tets(pos, sdf, msdf, tets, negate_msdf=False):
-    """Returns a dict with every tensor the reference returns (+ a few intermediates used by tests)."""
+def gshell_tets(pos, sdf, msdf, tets, negate_msdf=False, decisions=None):
+    """Returns a dict with every tensor the reference returns (+ a few intermediates used by tests).
+
+    A float64 evaluation (float64 `sdf`) keeps its values in float64.  Its occupancy is always taken on the float32 rounding of `sdf`; its
+    mSDF decisions -- which polygon corners lie inside (mocc3 / mocc4), which polygon edges are cut (the `ok` mask of cut_weights), hence `used`
+    and the cut faces -- are taken in the run's own dtype unless `decisions=` hands over the dict a float32 run of the same inputs returned:
+    then they are copied from that run, and the float64 run has the float32 run's topology by construction (the `ids=` idea of oracle/raster.py).
+    """
     sdf = sdf.reshape(-1)
-    if sdf.dtype != torch.float64:          # (a float64 evaluation keeps its values; its discrete decisions are taken on their float32 rounding)
+    if sdf.dtype != torch.float64:
         sdf = sdf.float()
+    dec = decisions['decisions'] if decisions is not None else None
     if negate_msdf:                       # hmsdf_tets_split.py:261-264 (type == "body"): negated INSIDE no_grad,
         msdf = (-msdf).detach()           # so the body pass sends no gradient to msdf (reference quirk, kept)
     with torch.no_grad():
@@ -162,15 +169,22 @@ def gshell_tets(pos, sdf, msdf, tets, negate_msdf=False):
         met = _t(MESH_EDGE_TABLE)
         loop3 = torch.gather(idx_map[one], 1, met[case[one]][:, [0, 1, 1, 2, 2, 0]]).view(-1, 3, 2)
         loop4 = torch.gather(idx_map[two], 1, met[case[two]][:, [0, 1, 1, 2, 2, 3, 3, 0]]).view(-1, 4, 2)
-        mocc3 = (msdf_vert[loop3[:, :, 0]] > 0).long()
-        mocc4 = (msdf_vert[loop4[:, :, 0]] > 0).long()
+        mocc3 = (msdf_vert[loop3[:, :, 0]] > 0).long() if dec is None else dec['mocc3']
+        mocc4 = (msdf_vert[loop4[:, :, 0]] > 0).long() if dec is None else dec['mocc4']
+        assert mocc3.shape == loop3.shape[:2] and mocc4.shape == loop4.shape[:2], 'decisions= of another input'
+    oks = {}
 
     def cut_weights(loop):
         m = msdf_vert[loop]                                              # [n, k, 2]
-        ok = torch.sign(m).sum(-1).abs() != 2
         a, b = m[..., 0], -m[..., 1]
         den = a + b
-        ok = ok & (den.abs() > 1e-12)
+        if dec is None:
+            ok = torch.sign(m).sum(-1).abs() != 2
+            ok = ok & (den.abs() > 1e-12)
+        else:
+            ok = dec['ok%d' % loop.shape[1]]
+            assert ok.shape == den.shape, 'decisions= of another input'
+        oks['ok%d' % loop.shape[1]] = ok.detach()
         den_safe = torch.where(ok, den, torch.ones_like(den))
         w0 = torch.where(ok, b / den_safe, torch.zeros_like(den))
         w1 = torch.where(ok, a / den_safe, torch.zeros_like(den))
@@ -218,6 +232,9 @@ def gshell_tets(pos, sdf, msdf, tets, negate_msdf=False):
         'msdf_boundary': msdf_aug_sg[n_wt:],
         # intermediates (not returned by the reference)
         'edge_verts': ev, 'v_nrm_watertight': v_nrm, 'msdf_vert': msdf_vert,
+        'decisions': {'mocc3': mocc3, 'mocc4': mocc4, **oks},
+        'bnd_edge': torch.cat([loop3.reshape(-1, 2), loop4.reshape(-1, 2)], 0), 'used': used,
+        'tet_case': torch.cat([case[one], case[two]]), 'poly_case': torch.cat([case3, case4]),
     }
 
 
