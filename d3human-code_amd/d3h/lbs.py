@@ -58,9 +58,11 @@ class KnnGrid:
 
     def query_counted(self, pts_cap, counts):
         """nearest template vertex of the first counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` (a buffer at its capacity), the row
-        count read on the DEVICE (d3h/mtets.py: work queued before the host knows the sizes of the extraction) -> idx [capacity] int32"""
+        count read on the DEVICE (d3h/mtets.py: work queued before the host knows the sizes of the extraction) -> idx [capacity] int32.
+        `counts`: the extraction's counter block of at least 11 int32 (entry 10 is its overflow flag: when set, nothing is written)"""
         lib = L.lib()
-        pts = pts_cap.detach()
+        pts = _capacity_points(pts_cap, 'query_counted')
+        _check_counts(counts, pts, 'query_counted')
         idx = torch.empty(pts.shape[0], dtype=torch.int32, device=pts.device)
         L.check(lib.d3h_knn1_grid_counted(L.ptr(pts), L.i32(pts.shape[0]), L.ptr(counts), L.ptr(self.cell_pts), L.ptr(self.cell_start),
                                           L.ptr(self.cell_seed), L.i32(self.nv), self.lo, L.f32(self.h), L.i32(self.g[0]), L.i32(self.g[1]),
@@ -89,11 +91,10 @@ class KnnGrid:
 
     def query_k_counted(self, pts_cap, counts, K, out=None):
         """query_k over the first counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` (a buffer at its capacity), the row count read on the
-        DEVICE -> KnnResult at the capacity; the other rows are not written (`out`: a KnnResult to write into)"""
+        DEVICE -> KnnResult at the capacity; the other rows are not written (`out`: a KnnResult to write into).  `counts`: as in query_counted"""
         pts = _knnk_args(pts_cap, K, convert=False)
         cap = pts.shape[0]
-        if counts.dtype != torch.int32 or counts.numel() < 11 or not counts.is_contiguous():
-            raise RuntimeError('d3h query_k_counted: counts must be the contiguous int32 counter block of the extraction')
+        _check_counts(counts, pts, 'query_k_counted')
         if out is None:
             out = KnnResult(torch.empty(cap, K, dtype=torch.int32, device=pts.device), torch.empty(cap, K, dtype=torch.float32, device=pts.device))
         _check_knn_result(out, cap, K, 'query_k_counted')
@@ -104,6 +105,38 @@ class KnnGrid:
 
 
 K_MAX = 32        # KNNK_MAX of csrc/lbs.hip
+J_MAX = 64        # MAXJ of csrc/lbs.hip
+N_COUNTS = 11     # counted_rows() of csrc/lbs.hip reads entries 0..2 (the row counts) and 10 (the extraction's overflow flag)
+
+
+def _check_counts(counts, pts, what):
+    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.numel() < N_COUNTS or \
+            not counts.is_contiguous() or counts.device != pts.device:
+        raise RuntimeError(f'd3h {what}: counts must be the extraction\'s contiguous int32 counter block of at least {N_COUNTS} entries on the '
+                           f'device of the points (the kernels read entries 0..2 and 10)')
+
+
+def _capacity_points(pts_cap, what):
+    pts = pts_cap.detach()
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous():
+        raise RuntimeError(f'd3h {what}: the capacity buffer must be contiguous float32 [capacity,3]')
+    return pts
+
+
+def _lbs_args(pts, idx, lbs_w, A0, A, trans, what):
+    """the checks of _lbsk_args for the K = 1 entry points: everything the kernels index with is checked on the host, before any launch"""
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise RuntimeError(f'd3h {what}: points must be [P,3], got {tuple(pts.shape)}')
+    P = pts.shape[0]
+    if not torch.is_tensor(idx) or idx.dtype != torch.int32 or tuple(idx.shape) != (P,) or not idx.is_contiguous() or idx.device != pts.device:
+        raise RuntimeError(f'd3h {what}: idx must be a contiguous int32 tensor of shape {(P,)} on the device of the points (knn1 returns one), got '
+                           f'{tuple(idx.shape)} {idx.dtype}')
+    if lbs_w.dim() != 2 or A0.dim() != 3 or tuple(A0.shape[1:]) != (4, 4) or A.dim() != 4 or tuple(A.shape[2:]) != (4, 4):
+        raise RuntimeError(f'd3h {what}: lbs_w [V,J], A0 [J,4,4] and A [B,J,4,4] expected, got {tuple(lbs_w.shape)}, {tuple(A0.shape)}, {tuple(A.shape)}')
+    nj, nb = lbs_w.shape[1], A.shape[0]
+    if not 1 <= nj <= J_MAX or A0.shape[0] != nj or A.shape[1] != nj or nb < 1 or \
+            trans.dim() not in (2, 3) or trans.shape[0] != nb or trans.shape[-1] != 3 or trans.numel() != nb * 3:
+        raise RuntimeError(f'd3h {what}: {nj} joints in lbs_w (1..{J_MAX}), A0 {tuple(A0.shape)}, A {tuple(A.shape)}, trans {tuple(trans.shape)}')
 
 
 class KnnResult:
@@ -228,20 +261,25 @@ def lbs_points(pts, idx, lbs_w, A0, A, trans, pre=None):
     """pts [P,3] canonical-mesh points, idx [P] nearest template vertex, lbs_w [V,J], A0 [J,4,4] init-pose transforms,
     A [B,J,4,4] frame transforms, trans [B,3]  ->  posed points [B,P,3].  `pre`: the result already computed by lbs_points_counted (the
     launch is skipped, the autograd node is the same)"""
+    _lbs_args(pts, idx, lbs_w, A0, A, trans, 'lbs_points')
     return _LBSFn.apply(pts, idx, lbs_w.contiguous().float(), A0, A, trans, pre)
 
 
 def lbs_points_counted(pts_cap, counts, idx_cap, lbs_w, A0, A, trans):
     """lbs_points over the first r = counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` [capacity, 3], r read on the DEVICE: the launch
     is queued before the host knows r.  -> a flat float buffer whose leading B * r * 3 floats are the dense [B, r, 3] result (narrow it with
-    counted_result once r is known and hand it to lbs_points(..., pre=))"""
+    counted_result once r is known and hand it to lbs_points(..., pre=)).  `counts`: the extraction's counter block of at least 11 int32;
+    entry 10 is its overflow flag: when set, nothing is written"""
     lib = L.lib()
+    pts = _capacity_points(pts_cap, 'lbs_points_counted')
+    _check_counts(counts, pts, 'lbs_points_counted')
+    _lbs_args(pts, idx_cap, lbs_w, A0, A, trans, 'lbs_points_counted')
     A0c = A0.detach().reshape(-1, 16).contiguous().float()
     Ac = A.detach().reshape(A.shape[0], -1, 16).contiguous().float()
     tr = trans.detach().reshape(-1, 3).contiguous().float()
     nb, nj, cap = Ac.shape[0], Ac.shape[1], pts_cap.shape[0]
     out = torch.empty(nb * cap * 3, dtype=torch.float32, device=pts_cap.device)
-    L.check(lib.d3h_lbs_fwd_counted(L.ptr(pts_cap.detach()), L.i32(cap), L.ptr(counts), L.ptr(idx_cap), L.ptr(lbs_w.contiguous().float()), L.i32(nj),
+    L.check(lib.d3h_lbs_fwd_counted(L.ptr(pts), L.i32(cap), L.ptr(counts), L.ptr(idx_cap), L.ptr(lbs_w.contiguous().float()), L.i32(nj),
                                     L.ptr(A0c), L.ptr(Ac), L.ptr(tr), L.i32(nb), L.ptr(out), L.stream()), 'lbs_fwd_counted')
     return out
 
@@ -312,11 +350,11 @@ def lbs_points_k(pts, nn, lbs_w, tmpl, A0, A, trans, pre=None):
 
 def lbs_points_k_counted(pts_cap, counts, nn_cap, lbs_w, tmpl, A0, A, trans):
     """lbs_points_k over the first r = counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` [capacity, 3] (nn_cap: query_k_counted of the same
-    buffer), r read on the DEVICE.  -> a flat float buffer whose leading B * r * 3 floats are the dense [B, r, 3] result (counted_result)"""
+    buffer), r read on the DEVICE.  -> a flat float buffer whose leading B * r * 3 floats are the dense [B, r, 3] result (counted_result).
+    `counts`: as in lbs_points_counted"""
     lib = L.lib()
-    pts = pts_cap.detach()
-    if pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous():
-        raise RuntimeError('d3h lbs_points_k_counted: the capacity buffer must be contiguous float32 [capacity,3]')
+    pts = _capacity_points(pts_cap, 'lbs_points_k_counted')
+    _check_counts(counts, pts, 'lbs_points_k_counted')
     cap = pts.shape[0]
     K, A0c, Ac, tr = _lbsk_args(nn_cap, lbs_w, tmpl, A0, A, trans, cap, 'lbs_points_k_counted')
     nb, nj = Ac.shape[0], Ac.shape[1]

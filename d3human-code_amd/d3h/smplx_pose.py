@@ -91,7 +91,36 @@ class _PoseFn(torch.autograd.Function):
         return d_fp, d_J, None
 
 
-def pose_transforms(full_pose, joints, parents32):
-    """full_pose [B,165] (or [B,55,3]) axis-angle, joints [B or 1,55,3] -> A [B,55,4,4] (lbs.py:311-413), one kernel launch"""
+NJ_MAX = 64       # NJ_MAX of csrc/smplx_pose.hip
+
+
+def check_tree(parents):
+    """parents of a kinematic tree as host values (a list, or a tensor: read back): 0 <= parents[j] < j for every j >= 1 (parents[0] is
+    ignored).  The backward folds the tree level by level from the leaves and relies on every ancestor walk ending at joint 0"""
+    p = [int(v) for v in (parents.tolist() if torch.is_tensor(parents) else parents)]
+    bad = [j for j in range(1, len(p)) if not 0 <= p[j] < j]
+    if bad:
+        raise ValueError(f'd3h pose_transforms: parents[j] must lie in 0..j-1 for every j >= 1; joint {bad[0]} has parent {p[bad[0]]}')
+
+
+def pose_transforms(full_pose, joints, parents32, tree_checked=False):
+    """full_pose [B,165] (or [B,55,3]) axis-angle, joints [B or 1,55,3] -> A [B,55,4,4] (lbs.py:311-413), one kernel launch.  Any tree of
+    1..64 joints: full_pose [B,3 nj] or [B,nj,3], joints [B or 1,nj,3], parents32 int32 [nj] on the device with parents[j] < j.  The values
+    of parents32 are read back and checked on every call (a host sync) unless `tree_checked`: the caller has run check_tree on the values
+    this tensor was built from (the body model does, once, when it is constructed)"""
+    if full_pose.dim() not in (2, 3) or full_pose.shape[-1] % 3 != 0 or (full_pose.dim() == 3 and full_pose.shape[2] != 3):
+        raise RuntimeError(f'd3h pose_transforms: the pose must be [B,3 J] or [B,J,3], got {tuple(full_pose.shape)}')
     B = full_pose.shape[0]
-    return _PoseFn.apply(full_pose.reshape(B, -1, 3), joints, parents32)
+    nj = full_pose.shape[1] if full_pose.dim() == 3 else full_pose.shape[1] // 3
+    if not 1 <= nj <= NJ_MAX:
+        raise RuntimeError(f'd3h pose_transforms: {nj} joints, the kernels hold 1..{NJ_MAX}')
+    if joints.dim() != 3 or joints.shape[0] not in (1, B) or tuple(joints.shape[1:]) != (nj, 3) or joints.device != full_pose.device:
+        raise RuntimeError(f'd3h pose_transforms: the rest joints must be [{B} or 1, {nj}, 3] on the device of the pose, got {tuple(joints.shape)}')
+    if not torch.is_tensor(parents32) or parents32.dtype != torch.int32 or tuple(parents32.shape) != (nj,) or not parents32.is_contiguous() or \
+            parents32.device != full_pose.device:
+        raise RuntimeError(f'd3h pose_transforms: parents must be a contiguous int32 tensor of shape {(nj,)} on {full_pose.device}, got '
+                           f'{tuple(parents32.shape) if torch.is_tensor(parents32) else type(parents32).__name__} '
+                           f'{getattr(parents32, "dtype", "")} on {getattr(parents32, "device", "")}')
+    if not tree_checked:
+        check_tree(parents32)
+    return _PoseFn.apply(full_pose.reshape(B, nj, 3), joints, parents32)

@@ -41,6 +41,7 @@ class SMPLX(torch.nn.Module):
         par = [int(p) for p in np.asarray(model_dict['parents'])]
         par[0] = -1
         self.register_buffer('parents', torch.tensor(par, dtype=torch.long))
+        SP.check_tree(par)                       # once, on the host: transforms() hands parents32 on as checked
         self.tree = SP.KinematicTree(par)
         self.register_buffer('parents32', torch.tensor([max(p_, 0) for p_ in par], dtype=torch.int32))
         # the joint regressor folded through the template and the blend-shape bases once: J = J0 + JD [betas, expr] (lbs.py:216-218 is
@@ -85,7 +86,7 @@ class SMPLX(torch.nn.Module):
             betas = betas.expand(B, -1)
         J = self.joints_fast(betas, expression.reshape(B, -1), face_offset, joint_offset, locator_offset)
         fp = SP.assemble_full_pose(global_orient, body_pose, jaw_pose, None, None, None, None)
-        return SP.pose_transforms(fp, J, self.parents32)
+        return SP.pose_transforms(fp, J, self.parents32, tree_checked=True)
 
     def transforms_reference(self, betas, global_orient, body_pose, jaw_pose, expression, face_offset=None, joint_offset=None,
                              locator_offset=None):
