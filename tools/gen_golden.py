@@ -1236,10 +1236,101 @@ def gen_texture2d():
     _savez_reproducible(os.path.join(GOLD, 'texture2d.npz'), npy(out))
 
 
+def gen_close_hole():
+    """reference script/connet_face_head.py (process_close_hole, :152-249) and the two open-edge functions of
+    script/process_body_cloth_head_msdfcut.py (find_open_edges :92-102, remove_faces_with_open_vertices :151-156) on the CPU, on the meshes
+    tests/meshtopo_cases.py generates.  openmesh, open3d, pymeshlab and pysdf are stubbed: om.read_trimesh serves the in-memory meshes, and a
+    TriangleMesh with the two open3d methods the script calls restates them from open3d's documented behaviour (exact coordinates, first
+    occurrence kept, order kept; triangles with two equal indices dropped).  Only inputs and outputs are recorded: arrays, the text of the `v`
+    lines the reference wrote, and the base names of the paths it returned."""
+    import tempfile
+    refharness.install()
+
+    class _Mesh:                                                    # what om.read_trimesh returns
+        def __init__(self, v, f):
+            self.v, self.f = v, f
+
+        def points(self):
+            return self.v
+
+        def face_vertex_indices(self):
+            return self.f
+
+    class TriangleMesh:
+        def __init__(self):
+            self.vertices, self.triangles = np.zeros((0, 3)), np.zeros((0, 3), np.int64)
+
+        def remove_duplicated_vertices(self):
+            first, new_index, keep = {}, [], []
+            for i, row in enumerate(np.asarray(self.vertices).tolist()):
+                if tuple(row) not in first:
+                    first[tuple(row)] = len(keep)
+                    keep.append(i)
+                new_index.append(first[tuple(row)])
+            self.vertices, self.triangles = np.asarray(self.vertices)[keep], np.asarray(new_index, np.int64)[np.asarray(self.triangles)]
+            return self
+
+        def remove_degenerate_triangles(self):
+            t = np.asarray(self.triangles)
+            self.triangles = t[(t[:, 0] != t[:, 1]) & (t[:, 1] != t[:, 2]) & (t[:, 2] != t[:, 0])]
+            return self
+
+    meshes, written = {}, {}
+    refharness.stub('openmesh', read_trimesh=lambda path: _Mesh(*meshes[os.path.basename(path)]))
+    refharness.stub('open3d')
+    refharness.stub('open3d.geometry', TriangleMesh=TriangleMesh)
+    refharness.stub('open3d.utility', Vector3dVector=lambda a: np.array(a, np.float64), Vector3iVector=lambda a: np.array(a, np.int64))
+    refharness.stub('open3d.io', write_triangle_mesh=lambda path, mesh: written.__setitem__(os.path.basename(path), mesh))
+    refharness.stub('pymeshlab')
+    refharness.stub('pysdf')
+    import script.connet_face_head as rcf
+    import script.process_body_cloth_head_msdfcut as rcut
+    assert rcf.__file__.startswith(refharness.REF) and rcut.__file__.startswith(refharness.REF)
+    sys.path.append(os.path.join(ROOT, 'd3human-code_amd'))        # AFTER the reference: the cases module imports d3h (it only generates inputs here)
+    sys.path.append(os.path.join(ROOT, 'tests'))
+    import meshtopo_cases as MC
+    out = {}
+    for name, (bv, bf, cv, cf, num) in MC.close_hole_scenarios().items():
+        meshes.clear()
+        written.clear()
+        meshes.update({'body.obj': (bv, bf.astype(np.int32)), 'cloth.obj': (cv, cf.astype(np.int32))})
+        with tempfile.TemporaryDirectory() as d:
+            ret = rcf.process_close_hole(None, d, os.path.join(d, 'body.obj'), os.path.join(d, 'cloth.obj'), num=num)
+            box = np.load(ret[2])
+            o = {'body_v': bv, 'body_f': bf, 'cloth_v': cv, 'cloth_f': cf, 'num': num, 'returned': np.array([os.path.basename(p) for p in ret]),
+                 'bbox_min': box['bbox_min'], 'bbox_max': box['bbox_max']}
+            vlines = {}
+            for part, src in (('body_frombody', 'body'), ('cloth_frombody', 'body'), ('body_fromcloth', 'cloth'), ('cloth_fromcloth', 'cloth')):
+                lines = open(os.path.join(d, part + '_faces.obj')).read().splitlines()
+                o[part + '_faces'] = np.array([[int(t) - 1 for t in ln.split()[1:]] for ln in lines if ln.startswith('f ')], np.int64).reshape(-1, 3)
+                text = '\n'.join(ln for ln in lines if ln.startswith('v '))
+                assert vlines.setdefault(src, text) == text
+            o['body_vlines'], o['cloth_vlines'] = np.array(vlines['body']), np.array(vlines['cloth'])
+            for side in ('cloth', 'body'):
+                m = written.get(side + '_concat.obj')
+                o[side + '_merged'] = m is not None
+                if m is not None:
+                    o[side + '_concat_v'], o[side + '_concat_f'] = np.asarray(m.vertices), np.asarray(m.triangles)
+        comps = rcf.filter_and_sort_components(rcf.find_connected_components(bv, bf))
+        ys = sorted(float(np.mean(bv[c], axis=0)[1]) for c in comps[:num])
+        assert ys[-1] - ys[-2] >= 0.1                               # the head choice must not hang on the summation order
+        print(f'close_hole {name}: body components {[len(c) for c in comps]} (first vertices {[c[0] for c in comps]}), returned {list(o["returned"])}, '
+              f'faces {[len(o[p + "_faces"]) for p in ("body_frombody", "cloth_frombody", "body_fromcloth", "cloth_fromcloth")]}, '
+              + ', '.join(f'{s}: {len(bv) + len(cv) - len(o[s + "_concat_v"])} welded, {len(o[s + "_concat_f"])} faces' for s in ('cloth', 'body') if o[s + '_merged']))
+        out.update({f'{name}.{k}': v for k, v in o.items()})
+    for name, (f, nv) in MC.open_edge_meshes().items():
+        ov, _ = rcut.find_open_edges(torch.from_numpy(f))
+        out.update({f'open.{name}.faces': f, f'open.{name}.nv': nv, f'open.{name}.open_vertices': np.array(ov, np.int64).reshape(-1),
+                    f'open.{name}.peeled': rcut.remove_faces_with_open_vertices(f, ov)})
+        print(f'close_hole open.{name}: {len(f)} faces, {len(ov)} open vertices, {len(out[f"open.{name}.peeled"])} faces left')
+    _savez_reproducible(os.path.join(GOLD, 'close_hole.npz'), npy(out))
+    print('close_hole.npz:', os.path.getsize(os.path.join(GOLD, 'close_hole.npz')), 'bytes')
+
+
 # dependency order: imgops / render read mtets_gshell_n8.npz, tick_split / tick_seq read tick_init.npz, tick_seq reads seq.npz (from GOLD)
 ALL = {'sdf_mlp': gen_sdf_mlp, 'mtets': gen_mtets, 'lbs': gen_lbs, 'imgops': gen_imgops, 'render': gen_render, 'seq': gen_seq, 'lpips': gen_lpips,
        'data_edges': gen_data_edges, 'tick_init': gen_tick_init, 'tick_split': gen_tick_split, 'tick_seq': gen_tick_seq,
-       'texture2d': gen_texture2d}
+       'texture2d': gen_texture2d, 'close_hole': gen_close_hole}
 
 if __name__ == '__main__':
     names = sys.argv[1:] or list(ALL)

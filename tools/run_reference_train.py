@@ -11,7 +11,9 @@ validate_all_mesh + the .ply / .npz outputs at the end).  optimize_mesh_seq loop
 shortens that by giving the train MODULE a `range` that yields the first `--iters` indices and the last one (the function, hence the
 file, is untouched; every statement of the loop body, the final validation and the delta / visible-triangle dump run).  All with
 `geometry`, `render` (`render.material` and `render.texture` included), `deform`, `nvdiffrast`, `tinycudann`, `kaolin`, `pytorch3d`, `ssim_loss`,
-`lap_loss` and `dataset` resolving to this build, and only `train` itself and `script` to the reference's files.  Inputs the
+`lap_loss`, `dataset` and `script.connet_face_head` resolving to this build, and only `train` itself and the rest of `script` to the reference's
+files.  --handoff (off by default): after the split stage the body and the garment mesh are extracted, written with the build's OBJ writer and
+handed to `train.process_close_hole` (train.py:1832-1843), which must be the build's; the six mesh files it leaves and the head box are read back.  Inputs the
 repository does not ship are synthetic: the sequence (the build's Dataset_split over an in-memory frame), the SMPL-X model (d3h.synth), the tet grid, the merged body + garment mesh of the seq stage (an ellipsoid and an open tube, labels
 prepared as train.py:1885-1911 does).  Third-party modules that train.py imports at the top but these stages never call
 (xatlas, cv2, openmesh, tensorboardX, imageio, open3d, pymeshlab, pysdf, trimesh, torchvision) are stubbed when absent.
@@ -65,6 +67,7 @@ def main():
     ap.add_argument('--emulator', action='store_true')
     ap.add_argument("--eik", type=int, default=256)
     ap.add_argument("--out", default=None)
+    ap.add_argument('--handoff', action='store_true', help='after the split stage: write its body and garment meshes and run train.process_close_hole on them')
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -174,6 +177,38 @@ def main():
         # the split stage's optimiser holds no SDF-network parameter (train.py:887-902): it must not have moved
         assert all(torch.equal(p.detach(), q) for p, q in zip(geometry_obj.sdf_net.parameters(), sd0))
         assert finite()
+        if a.handoff:
+            # train.py:1832-1843: the split stage's body and garment meshes go to disk and process_close_hole sorts their components
+            from render import obj as robj
+            import script.connet_face_head as cfh
+            assert os.path.relpath(cfh.__file__, ROOT).startswith('d3human-code_amd') and train.process_close_hole is cfh.process_close_hole, \
+                'train.process_close_hole is not the build\'s script/connet_face_head.py'
+            with torch.no_grad():
+                # A handful of iterations from hmsdf.py:311's start (mSDF positive almost everywhere) have not formed a partition: the body pass
+                # extracts a sliver or nothing, and process_close_hole -- the reference's too -- has no head to box.  The meshes are extracted
+                # under the partition d3h.scene gives the split stage (garment on the torso band, a seeded ripple); the fitted mSDF is put back.
+                fitted = geometry_obj.msdf.detach().clone()
+                y = geometry_obj.verts[:, 1]
+                band = ((y > -0.75) & (y < 0.05)).float() * 2 - 1
+                ripple = torch.rand(y.shape[0], generator=torch.Generator().manual_seed(17)).to(y.device) - 0.5
+                geometry_obj.msdf.data.copy_((0.5 * band + 0.04 * ripple).clamp(-1, 1))
+                for part in ('body', 'cloth'):
+                    robj.write_obj(folder=out, save_name=f'split_{part}_imesh_{a.iters - 1}.obj', save_material=False,
+                                   mesh=geometry_obj.getMesh_split(mat, part, it=a.iters - 1)['imesh'])
+                geometry_obj.msdf.data.copy_(fitted)
+            closehole_root = os.path.join(out, 'close_hole_split_cloth0')
+            os.makedirs(closehole_root, exist_ok=True)
+            body_path, cloth_path, bbox_path = train.process_close_hole(F, closehole_root, os.path.join(out, f'split_body_imesh_{a.iters - 1}.obj'),
+                                                                         os.path.join(out, f'split_cloth_imesh_{a.iters - 1}.obj'), num=5)
+            box = np.load(bbox_path)
+            assert box['bbox_min'].shape == (3,) and (box['bbox_min'] < box['bbox_max']).all()
+            parsed = {}
+            for p in [os.path.join(closehole_root, n + '_faces.obj') for n in ('body_frombody', 'cloth_frombody', 'body_fromcloth', 'cloth_fromcloth')] + \
+                    [body_path, cloth_path]:
+                v_, f_ = cfh.om_loadmesh(p)
+                assert v_.shape[0] > 0 and (f_.size == 0 or (f_.min() >= 0 and f_.max() < v_.shape[0])), p
+                parsed[os.path.basename(p)] = (v_.shape[0], f_.shape[0])
+            print('process_close_hole returned', os.path.basename(body_path), os.path.basename(cloth_path), os.path.basename(bbox_path), '; (vertices, faces):', parsed)
     if 'seq' in stages:
         import builtins
         from render import mesh as rmesh
