@@ -20,6 +20,9 @@
 // MI355X design notes: triangles are rasterised one WAVE each (wave-uniform set-up, 64 lanes sweep the bounding box) straight
 // into a 64-bit (depth | id) buffer with atomicMin, then one coalesced per-pixel resolve pass computes barycentrics and
 // derivatives.  All image-space passes are HBM-streaming: 16-B pixel records, NHWC, one pass each.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include "d3h_common.h"
 #include "composite.h"
 
@@ -931,6 +934,198 @@ __global__ __launch_bounds__(256) void gbuffer_bwd_kernel(const float* __restric
     }
 }
 
+// ---- the same backward with the sums taken per workgroup in LDS ---------------------------------------------------------------------
+// gbuffer_bwd_kernel above is bound by memory-side float atomics: a workgroup owns 256 pixels of ONE row, a triangle of ~30 pixels spans
+// 5-6 rows, so every triangle is cut into many runs and each run tail issues, per vertex and channel, a single-lane atomic (a 64-B request
+// for 4 useful bytes).  The destinations are few (vertices x (na + 3) floats), so here a workgroup owns a 2-D TW x TH tile of one frame, the
+// run tails add into an LDS table keyed by vertex index (one row of na d(attr) floats + d(pos) x, y, w when RAST per slot; a second small
+// table keyed by face id for d(face)), and after a barrier consecutive lanes flush consecutive floats of a slot's row: one atomic
+// wave-instruction covers whole rows.  A key that finds no slot within GBL_PROBES steps (table full) sends its contribution straight to
+// global memory with the atomics of the kernel above: no spin-wait anywhere, every path ends for any input.
+constexpr int GBL_VCAP = 256, GBL_VPOOL = 4096;     // vertex table: slots (power of two), floats (256 slots of up to 16 floats)
+constexpr int GBL_FCAP = 256, GBL_FPOOL = 1024;     // face table
+constexpr int GBL_PROBES = 8;
+constexpr int GBL_SLOTS = 64;                       // slots in use by default (a 16 x 16 tile of the flagship frames sees ~25 vertices)
+
+// slot of `key` (>= 0) in an open-addressing table of `cap` (power of two, or 0 = no table) LDS keys initialised to -1; -1 = no slot found
+__device__ __forceinline__ int gbl_claim(int* keys, int cap, int key) {
+    if (cap == 0) return -1;
+    int s = (int)(((unsigned)key * 0x9E3779B1u) >> 16) & (cap - 1);
+    for (int p = 0; p < GBL_PROBES && p < cap; ++p) {
+        const int old = atomicCAS(&keys[s], -1, key);
+        if (old == -1 || old == key) return s;
+        s = (s + 1) & (cap - 1);
+    }
+    return -1;
+}
+
+template <bool RAST, int TW, int TH>
+__global__ __launch_bounds__(256) void gbuffer_bwd_tile_kernel(const float* __restrict__ attr, int attr_bstride, int na, int face_bstride, int fw,
+                                                               const float* __restrict__ rast, const int* __restrict__ tri, GbufGrad gg,
+                                                               float* __restrict__ d_attr, float* __restrict__ d_face, float* __restrict__ d_rast,
+                                                               const float* __restrict__ pos, int pos_bstride, int H, int W,
+                                                               float* __restrict__ d_pos, int vcap, int fcap) {
+    static_assert((TW * TH) % 256 == 0 && TW <= 256 && 256 % TW == 0, "a pass of the workgroup covers whole tile rows");
+    __shared__ __attribute__((aligned(16))) float vval[GBL_VPOOL];
+    __shared__ __attribute__((aligned(16))) float fval[GBL_FPOOL];
+    __shared__ int vkey[GBL_VCAP];
+    __shared__ int fkey[GBL_FCAP];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int b = blockIdx.z;
+    const int na_v = d_attr ? na : 0;                       // floats of a vertex slot: d(attr) row, then d(pos) x, y, w
+    const int vstride = na_v + (RAST ? 3 : 0);
+    const bool want_face = gg.g_face && d_face;
+    // Most tiles of a frame see no triangle: they leave after a vote (and their zeros of d_rast), without touching the tables.
+    __shared__ int s_any;
+    if (tid == 0) s_any = 0;
+    __syncthreads();
+    {
+        bool any = false;
+        for (int pass = 0; pass < TW * TH / 256; ++pass) {
+            const int lp = pass * 256 + tid;
+            const int px = blockIdx.x * TW + lp % TW, py = blockIdx.y * TH + lp / TW;
+            if (px < W && py < H) any = any || rast[4 * (((size_t)b * H + py) * W + px) + 3] > 0.f;
+        }
+        if (any) s_any = 1;
+    }
+    __syncthreads();
+    if (!s_any) {
+        if (d_rast) {
+            for (int pass = 0; pass < TW * TH / 256; ++pass) {
+                const int lp = pass * 256 + tid;
+                const int px = blockIdx.x * TW + lp % TW, py = blockIdx.y * TH + lp / TW;
+                if (px < W && py < H) *(float4*)(d_rast + 4 * (((size_t)b * H + py) * W + px)) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        return;
+    }
+    // (the pools are multiples of four floats: the rounded-up tail of the last float4 stays inside them)
+    for (int k = tid; k < vcap; k += 256) vkey[k] = -1;
+    for (int k = 4 * tid; k < vcap * vstride; k += 1024) *(float4*)&vval[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (want_face) {
+        for (int k = tid; k < fcap; k += 256) fkey[k] = -1;
+        for (int k = 4 * tid; k < fcap * fw; k += 1024) *(float4*)&fval[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    const float* ab = attr + (size_t)b * attr_bstride;
+    float* db_ = d_attr ? d_attr + (size_t)b * attr_bstride : nullptr;
+    float* dfb = want_face ? d_face + (size_t)b * face_bstride : nullptr;
+    float* dpb = RAST ? d_pos + (size_t)b * pos_bstride : nullptr;
+#pragma unroll 1
+    for (int pass = 0; pass < TW * TH / 256; ++pass) {
+        const int lp = pass * 256 + tid;
+        const int px = blockIdx.x * TW + lp % TW, py = blockIdx.y * TH + lp / TW;
+        const bool inb = px < W && py < H;
+        const size_t i = ((size_t)b * H + (inb ? py : 0)) * W + (inb ? px : 0);
+        float4 r = inb ? *(const float4*)(rast + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int id = (int)r.w;
+        const bool hit = id > 0;
+        if (__ballot(hit) == 0ull) {            // wave-uniform: nothing covered here
+            if (d_rast && inb) *(float4*)(d_rast + 4 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const D3hSeg sg = d3h_seg_runs(hit ? id : -1, lane);               // runs of lanes on one triangle (the tile is in one frame)
+        const bool tail = sg.tail && hit;
+        float gu = 0.f, gv = 0.f;
+        const int f = hit ? id - 1 : 0;
+        int vi[3] = {0, 0, 0};
+        if (hit) { vi[0] = tri[3 * (size_t)f]; vi[1] = tri[3 * (size_t)f + 1]; vi[2] = tri[3 * (size_t)f + 2]; }
+        const size_t i0 = (size_t)vi[0] * na, i1 = (size_t)vi[1] * na, i2 = (size_t)vi[2] * na;
+        int sl[3] = {-1, -1, -1};                                           // the run tail's slots of its three vertices
+        if (tail && vstride > 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sl[k] = gbl_claim(vkey, vcap, vi[k]);
+        }
+        const float u = r.x, v = r.y;
+        int c0 = 0;
+#pragma unroll
+        for (int g = 0; g < GBUF_GROUPS; ++g) {
+            const int wd = gg.width[g];
+            if (gg.g[g]) {
+                for (int c = 0; c < wd; ++c) {
+                    float gc = hit ? gg.g[g][i * wd + c] : 0.f;
+                    const int ch = c0 + c;
+                    if (db_) {
+                        float s0 = d3h_seg_sum(gc * u, lane, sg.start);
+                        float s1 = d3h_seg_sum(gc * v, lane, sg.start);
+                        float s2 = d3h_seg_sum(gc * (1.0f - u - v), lane, sg.start);
+                        if (tail) {
+                            if (s0 != 0.f) { if (sl[0] >= 0) atomicAdd(&vval[sl[0] * vstride + ch], s0); else atomicAdd(db_ + i0 + ch, s0); }
+                            if (s1 != 0.f) { if (sl[1] >= 0) atomicAdd(&vval[sl[1] * vstride + ch], s1); else atomicAdd(db_ + i1 + ch, s1); }
+                            if (s2 != 0.f) { if (sl[2] >= 0) atomicAdd(&vval[sl[2] * vstride + ch], s2); else atomicAdd(db_ + i2 + ch, s2); }
+                        }
+                    }
+                    if (hit && gc != 0.f) {
+                        float x2 = ab[i2 + ch];
+                        gu = fmaf(gc, ab[i0 + ch] - x2, gu);
+                        gv = fmaf(gc, ab[i1 + ch] - x2, gv);
+                    }
+                }
+            }
+            c0 += wd;
+        }
+        if (want_face) {                        // u + v + (1 - u - v) of the gradient lands on the one face row; no barycentric gradient
+            const int sf = tail ? gbl_claim(fkey, fcap, f) : -1;
+            for (int c = 0; c < fw; ++c) {
+                float gc = hit ? gg.g_face[i * fw + c] : 0.f;
+                float s = d3h_seg_sum(gc * u, lane, sg.start) + d3h_seg_sum(gc * v, lane, sg.start) + d3h_seg_sum(gc * (1.0f - u - v), lane, sg.start);
+                if (tail && s != 0.f) { if (sf >= 0) atomicAdd(&fval[sf * fw + c], s); else atomicAdd(dfb + (size_t)f * fw + c, s); }
+            }
+        }
+        if (d_rast && inb) *(float4*)(d_rast + 4 * i) = make_float4(gu, gv, 0.f, 0.f);
+        if (RAST) {
+            const bool live = hit && !(gu == 0.f && gv == 0.f);
+            if (__ballot(live) == 0ull) continue;           // wave-uniform
+            float out[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            int vj[3];
+            if (live) raster_bwd_pixel(pos + (size_t)b * pos_bstride, tri, f, px, py, H, W, gu, gv, out, vj);
+            // (the runs are those of the covered lanes, every lane of a run on triangle f: lanes without a barycentric gradient add zeros)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float sx = d3h_seg_sum(out[3 * k + 0], lane, sg.start);
+                const float sy = d3h_seg_sum(out[3 * k + 1], lane, sg.start);
+                const float sw = d3h_seg_sum(out[3 * k + 2], lane, sg.start);
+                if (tail && (sx != 0.f || sy != 0.f || sw != 0.f)) {
+                    if (sl[k] >= 0) {
+                        float* dv = &vval[sl[k] * vstride + na_v];
+                        atomicAdd(dv + 0, sx);
+                        atomicAdd(dv + 1, sy);
+                        atomicAdd(dv + 2, sw);
+                    } else {
+                        float* dp = dpb + 4 * (size_t)vi[k];
+                        atomicAdd(dp + 0, sx);
+                        atomicAdd(dp + 1, sy);
+                        atomicAdd(dp + 3, sw);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // flush: consecutive lanes take consecutive floats of a slot's row; zero entries (and empty slots, which are all zero) are skipped
+    // (16 lanes per slot: unused slots cost one key read)
+    for (int k = tid; k < vcap * 16; k += 256) {
+        const int slot = k >> 4, key = vkey[slot];
+        if (key < 0) continue;
+        for (int c = k & 15; c < vstride; c += 16) {
+            const float s = vval[slot * vstride + c];
+            if (s == 0.f) continue;
+            if (c < na_v) atomicAdd(db_ + (size_t)key * na + c, s);
+            else if (RAST) atomicAdd(dpb + 4 * (size_t)key + (c - na_v == 2 ? 3 : c - na_v), s);
+        }
+    }
+    if (want_face) {
+        for (int k = tid; k < fcap * 4; k += 256) {
+            const int slot = k >> 2, key = fkey[slot];
+            if (key < 0) continue;
+            for (int c = k & 3; c < fw; c += 4) {
+                const float s = fval[slot * fw + c];
+                if (s != 0.f) atomicAdd(dfb + (size_t)key * fw + c, s);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // antialias
 // ------------------------------------------------------------------------------------------------
@@ -1794,6 +1989,37 @@ extern "C" int d3h_gbuffer_fwd(const float* attr, int attr_bstride, int na, cons
     return D3H_OK;
 }
 
+// The LDS-summing backward (gbuffer_bwd_tile_kernel), unless switched off.  Read per call, for A/B runs and tests in one process:
+//   D3H_GBUF_LDS=0        the per-row kernel (returns false: the caller launches it)
+//   D3H_GBUF_TILE=WxH     tile shape: 16x16 (default), 32x8, 64x4, 8x32, 32x32 (4 pixels per thread)
+//   D3H_GBUF_LDS_SLOTS=n  at most n slots per table (rounded down to a power of two; 0: every contribution takes the direct-atomic path);
+//                         default GBL_SLOTS -- the tuning table is in profiles/image_bwd_tail_ab.txt
+static inline int gbl_pow2_floor(int v) { int p = 0; for (int q = 1; q > 0 && q <= v; q <<= 1) p = q; return p; }
+template <bool RAST>
+static bool gbuffer_bwd_tile_launch(const float* attr, int attr_bstride, int na, int face_bstride, int fw, const float* rast, const int* tri, int nb,
+                                    int H, int W, const GbufGrad& gg, float* d_attr, float* d_face, float* d_rast, const float* pos, int pos_bstride,
+                                    float* d_pos, hipStream_t s) {
+    const char* e = getenv("D3H_GBUF_LDS");
+    if ((e && e[0] == '0') || nb > 65535) return false;
+    e = getenv("D3H_GBUF_LDS_SLOTS");
+    const int limit = e ? atoi(e) : GBL_SLOTS;
+    const int vstride = (d_attr ? na : 0) + (RAST ? 3 : 0);
+    const int vcap = (vstride > 0 && limit > 0) ? gbl_pow2_floor(std::min(std::min(limit, GBL_VCAP), GBL_VPOOL / vstride)) : 0;
+    const int fcap = (fw > 0 && limit > 0) ? gbl_pow2_floor(std::min(std::min(limit, GBL_FCAP), GBL_FPOOL / fw)) : 0;
+    e = getenv("D3H_GBUF_TILE");
+    const int tw = e ? atoi(e) : 16, th = (e && strchr(e, 'x')) ? atoi(strchr(e, 'x') + 1) : 16;
+#define GBL_LAUNCH(TW, TH)                                                                                                                         \
+    hipLaunchKernelGGL((gbuffer_bwd_tile_kernel<RAST, TW, TH>), dim3(d3h_cdiv(W, TW), d3h_cdiv(H, TH), nb), dim3(256), 0, s, attr, attr_bstride, na, \
+                       face_bstride, fw, rast, tri, gg, d_attr, d_face, d_rast, pos, pos_bstride, H, W, d_pos, vcap, fcap)
+    if (tw == 64 && th == 4) GBL_LAUNCH(64, 4);
+    else if (tw == 8 && th == 32) GBL_LAUNCH(8, 32);
+    else if (tw == 32 && th == 32) GBL_LAUNCH(32, 32);
+    else if (tw == 32 && th == 8) GBL_LAUNCH(32, 8);
+    else GBL_LAUNCH(16, 16);
+#undef GBL_LAUNCH
+    return true;
+}
+
 // g_k: upstream gradient of group k (NULL = zero); d_attr, d_face accumulated (caller zero-fills; may be NULL); d_rast [nb][H][W][4]
 // overwritten (may be NULL)
 extern "C" int d3h_gbuffer_bwd(const float* attr, int attr_bstride, int na, int face_bstride, int fw, const float* rast, const int* tri, int nb,
@@ -1804,8 +2030,10 @@ extern "C" int d3h_gbuffer_bwd(const float* attr, int attr_bstride, int na, int 
     if (n == 0) return D3H_OK;
     GbufGrad gg{{g0, g1, g2, g3}, {w0, w1, w2, w3}, g_face};
     const int kt = d3h_ktime_begin(D3H_KT_GBUFFER_BWD, (long long)n, (hipStream_t)stream);
-    hipLaunchKernelGGL((gbuffer_bwd_kernel<false>), dim3(d3h_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attr, attr_bstride, na, face_bstride, fw,
-                       rast, tri, n, npb, gg, d_attr, d_face, d_rast, (const float*)nullptr, 0, H, W, (float*)nullptr);
+    if (!gbuffer_bwd_tile_launch<false>(attr, attr_bstride, na, face_bstride, fw, rast, tri, nb, H, W, gg, d_attr, d_face, d_rast, nullptr, 0, nullptr,
+                                        (hipStream_t)stream))
+        hipLaunchKernelGGL((gbuffer_bwd_kernel<false>), dim3(d3h_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attr, attr_bstride, na, face_bstride,
+                           fw, rast, tri, n, npb, gg, d_attr, d_face, d_rast, (const float*)nullptr, 0, H, W, (float*)nullptr);
     d3h_ktime_end(kt, (hipStream_t)stream);
     D3H_LAUNCH_CHECK();
     return D3H_OK;
@@ -1823,8 +2051,10 @@ extern "C" int d3h_gbuffer_raster_bwd(const float* attr, int attr_bstride, int n
     if (n == 0) return D3H_OK;
     GbufGrad gg{{g0, g1, g2, g3}, {w0, w1, w2, w3}, g_face};
     const int kt = d3h_ktime_begin(D3H_KT_GBUFFER_BWD, (long long)n, (hipStream_t)stream);
-    hipLaunchKernelGGL((gbuffer_bwd_kernel<true>), dim3(d3h_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attr, attr_bstride, na, face_bstride, fw,
-                       rast, tri, n, npb, gg, d_attr, d_face, (float*)nullptr, pos, pos_bstride, H, W, d_pos);
+    if (!gbuffer_bwd_tile_launch<true>(attr, attr_bstride, na, face_bstride, fw, rast, tri, nb, H, W, gg, d_attr, d_face, nullptr, pos, pos_bstride, d_pos,
+                                       (hipStream_t)stream))
+        hipLaunchKernelGGL((gbuffer_bwd_kernel<true>), dim3(d3h_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, attr, attr_bstride, na, face_bstride,
+                           fw, rast, tri, n, npb, gg, d_attr, d_face, (float*)nullptr, pos, pos_bstride, H, W, d_pos);
     d3h_ktime_end(kt, (hipStream_t)stream);
     D3H_LAUNCH_CHECK();
     return D3H_OK;

@@ -73,6 +73,57 @@ __device__ __forceinline__ void encode(const GridCfg& g, const float* __restrict
     }
 }
 
+// encode() (same operations in the same order: bit-equal enc) that also parks the lane's 30 derivative weights d(enc_c) / d(xn_d) =
+// scale_l * sum over corners of dw/dfr_d * table value, while the corners are in registers: dE[(3 c + d) * 64] (the caller passes its own
+// lane's column of a wave-private [30][64] LDS tile).  ins[d] = 1, or 0 for a clamped coordinate (!inside[d]), which parks exact zeros.
+__device__ __forceinline__ void encode_dx(const GridCfg& g, const float* __restrict__ table, const float (&xn)[3], const float (&ins)[3],
+                                          float (&enc)[ENC], float* dE) {
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        float p[3], fr[3];
+        int pg[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            p[d] = fmaf(xn[d], g.scale[l], 0.5f);
+            float fl = floorf(p[d]);
+            fr[d] = p[d] - fl;
+            pg[d] = (int)fl;
+        }
+        float f0 = 0.f, f1 = 0.f, d0[3] = {0.f, 0.f, 0.f}, d1[3] = {0.f, 0.f, 0.f};
+        const int res = g.res[l];
+        const float2* tab = (const float2*)table;        // (one base + a 32-bit entry offset: five per-level base pointers held over the caller's loop cost 10 scalar registers)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            float w = 1.f, wd[3];
+            int idx = 0, stride = 1;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                int bit = (c >> d) & 1;
+                wd[d] = bit ? fr[d] : (1.f - fr[d]);
+                w *= wd[d];
+                idx += (pg[d] + bit) * stride;
+                stride *= res;
+            }
+            if (idx >= g.size[l]) idx -= g.size[l];     // only x == 1 on level 0 (scale 15 -> corner 16) can wrap
+            float2 v = tab[g.offset[l] + idx];
+            f0 = fmaf(w, v.x, f0);
+            f1 = fmaf(w, v.y, f1);
+            const float dw[3] = {(c & 1) ? wd[1] * wd[2] : -(wd[1] * wd[2]), (c & 2) ? wd[0] * wd[2] : -(wd[0] * wd[2]),
+                                 (c & 4) ? wd[0] * wd[1] : -(wd[0] * wd[1])};
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { d0[d] = fmaf(dw[d], v.x, d0[d]); d1[d] = fmaf(dw[d], v.y, d1[d]); }
+        }
+        enc[2 * l] = f0;
+        enc[2 * l + 1] = f1;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float s = g.scale[l] * ins[d];
+            dE[(3 * (2 * l) + d) * 64] = d0[d] * s;
+            dE[(3 * (2 * l + 1) + d) * 64] = d1[d] * s;
+        }
+    }
+}
+
 __device__ __forceinline__ bool normalise(const TexParams& tp, const float* __restrict__ x, float (&xn)[3], bool (&inside)[3]) {
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
@@ -725,15 +776,22 @@ __device__ __forceinline__ D3hH2Frag tex_h2_image_frag(const float* T, int row, 
 // THE CO-RESIDENCY RULE (csrc/sdf_mlp_x3.h): a kernel that issues 16-bit MFMAs back to back must not share a SIMD with a wave of another kernel
 // (packed-f32 VALU results of the foreign wave go wrong in lanes 48..63): 512-thread workgroups with all 256 VGPRs claimed -- two waves per
 // SIMD own the register file -- and a workgroup barrier after the last MFMA (the flush below).  tests/test_mfma_claim.py checks both in the ISA.
+template <bool DX>      // DX: also write the position gradient d_x (below); without it: encode() and no derivative tile (94 KB of LDS instead of 152)
 __global__ __launch_bounds__(512) void texmlp_bwd_mlp_h2_kernel(GridCfg g, TexParams tp, const float* __restrict__ x, const float* __restrict__ mask,
                                                                 const float* __restrict__ table, const float* __restrict__ w, int64_t n,
-                                                                const float* __restrict__ g_out, float* __restrict__ d_w, float* __restrict__ genc) {
+                                                                const float* __restrict__ g_out, float* __restrict__ d_w, float* __restrict__ genc,
+                                                                float* __restrict__ d_x) {
     __shared__ __attribute__((aligned(16))) float smem[8 * 2 * 32 * HP];          // the transposition images (8 waves x 2 x 32 x HP) and, at the end, the flush
     static_assert(4 * 3 * 1024 <= 8 * 2 * 32 * HP, "the flush buffer lives in the images");
+    // d_x: the position gradient comes out of this kernel too -- d_x = sum_c d(enc_c)/dx * GE_c needs the corner values of the encoding and GE,
+    // and both exist here.  The 30 derivative weights of a pixel are formed while encode has its corners in registers and wait in a
+    // wave-private [30][64] tile (7.5 KB per wave) until the chain has produced GE: no second gather pass over the table, no read-back of genc.
+    __shared__ float sDE[DX ? 8 : 1][DX ? 3 * ENC * 64 : 1];
 #ifndef D3H_EMULATED
     asm volatile("v_mov_b32 v255, 0" ::: "v255");
 #endif
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
+    // (the wave index as a scalar: the tile loop and its early exits are then scalar branches -- no saved exec masks held over the loop)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
     float* TA = smem + (wave * 2 + 0) * 32 * HP;
     float* TB = smem + (wave * 2 + 1) * 32 * HP;
     const float* w1 = w;
@@ -777,12 +835,21 @@ __global__ __launch_bounds__(512) void texmlp_bwd_mlp_h2_kernel(GridCfg g, TexPa
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc1[r] = 0.f; acc2[r] = 0.f; acc3[r] = 0.f; }
     const f32x16 zero16 = acc1;
-    const int64_t nwt = (n + 63) / 64;
-    for (int64_t wt = (int64_t)blockIdx.x * 8 + wave; wt < nwt; wt += (int64_t)gridDim.x * 8) {
-        const int64_t p0 = wt * 64;
+    // the output ranges of this lane's channels r + 4 h, in four registers (as 12 scalars held over the loop they pushed the kernel into spills)
+    float rng[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int c1 = r + 4 < OUTC ? r + 4 : 0;
+        const float lo_half = tp.omax[r] - tp.omin[r], hi_half = r + 4 < OUTC ? tp.omax[c1] - tp.omin[c1] : 0.f;
+        rng[r] = h == 0 ? lo_half : hi_half;
+    }
+    const int nwt = (int)((n + 63) / 64);            // (32-bit tile counters: the entry point refuses n >= 2^36)
+    for (int wt = (int)blockIdx.x * 8 + wave; wt < nwt; wt += (int)gridDim.x * 8) {
+        const int64_t p0 = (int64_t)wt * 64;
         const int64_t i = p0 + lane;
         const bool active = (i < n) && !(mask && !(mask[i] > 0.f));
         const unsigned long long am = __ballot(active);
+        if (DX && !active && i < n) { d_x[3 * i] = 0.f; d_x[3 * i + 1] = 0.f; d_x[3 * i + 2] = 0.f; }      // masked pixels: zero
         if (am == 0ull) continue;                                // wave-uniform: nothing covered in these 64 pixels
         float xn[3] = {0.f, 0.f, 0.f}, enc[ENC];
         bool inside[3] = {false, false, false};
@@ -790,8 +857,14 @@ __global__ __launch_bounds__(512) void texmlp_bwd_mlp_h2_kernel(GridCfg g, TexPa
         for (int c = 0; c < ENC; ++c) enc[c] = 0.f;
         if (active) {
             normalise(tp, x + 3 * i, xn, inside);
-            encode(g, table, xn, enc);
+            if (DX) {
+                const float ins[3] = {inside[0] ? 1.f : 0.f, inside[1] ? 1.f : 0.f, inside[2] ? 1.f : 0.f};
+                encode_dx(g, table, xn, ins, enc, sDE[wave] + lane);
+            } else {
+                encode(g, table, xn, enc);
+            }
         }
+        if (DX) D3H_WAVE_SYNC();                                 // the chains read other lanes' columns of sDE
         float eo[ENC];                                           // the encoding of the pixel in the other lane half
 #pragma unroll
         for (int c = 0; c < ENC; ++c) eo[c] = __shfl_xor(enc[c], 32);
@@ -837,7 +910,7 @@ __global__ __launch_bounds__(512) void texmlp_bwd_mlp_h2_kernel(GridCfg g, TexPa
                 const int c = r + 4 * h;
                 if (c < OUTC && pact) {
                     const float sg = 1.f / (1.f + expf(-Z3[r]));
-                    go[r] = g_out[pp * OUTC + c] * (tp.omax[c] - tp.omin[c]) * sg * (1.f - sg);
+                    go[r] = g_out[pp * OUTC + c] * rng[r] * sg * (1.f - sg);
                     const float a = fabsf(go[r]);
                     gmax = (a < 3.0e38f) ? fmaxf(gmax, a) : gmax;
                 }
@@ -851,6 +924,7 @@ __global__ __launch_bounds__(512) void texmlp_bwd_mlp_h2_kernel(GridCfg g, TexPa
                         const int row = rho(r, h);
                         if (row < ENC) genc[pp * ENC + row] = 0.f;
                     }
+                    if (DX && h == 0) { d_x[3 * pp] = 0.f; d_x[3 * pp + 1] = 0.f; d_x[3 * pp + 2] = 0.f; }
                 }
                 continue;
             }
@@ -892,6 +966,27 @@ __global__ __launch_bounds__(512) void texmlp_bwd_mlp_h2_kernel(GridCfg g, TexPa
                 for (int r = 0; r < 16; ++r) {
                     const int row = rho(r, h);
                     if (row < ENC) genc[pp * ENC + row] = GE[r] * sc;
+                }
+            }
+            if (DX) {
+                // d_x of pixel pp: its derivative weights are in column 32 ch + m of the wave's tile, its GE rows split over the two lane halves
+                const float* dE = sDE[wave] + 32 * ch + m;
+                const float sc = tp.in_grad_scale * Si;
+                float gx[3] = {0.f, 0.f, 0.f};
+                // rows rho(r, h) < 10: registers 0 .. 3 are rows r + 4 h in both halves, registers 4, 5 rows 8, 9 in half 0 only
+                static_assert(ENC == 10, "the row split below");
+#pragma unroll
+                for (int r = 0; r < 6; ++r) {
+                    const int row = r < 4 ? r + 4 * h : 4 + r;
+                    const float ge = (pact && (r < 4 || h == 0)) ? GE[r] * sc : 0.f;         // (the value written to genc)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) gx[d] = fmaf(dE[(3 * row + d) * 64], ge, gx[d]);
+                }
+#pragma unroll
+                for (int d = 0; d < 3; ++d) gx[d] += __shfl_xor(gx[d], 32);
+                if (pact && h == 0) {
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) d_x[3 * pp + d] = gx[d] / (tp.b1[d] - tp.b0[d]);
                 }
             }
             if (d_w) {
@@ -1051,7 +1146,7 @@ extern "C" int d3h_texmlp_fwd(const float* x, const float* mask, const float* ta
 extern "C" int d3h_texmlp_bwd(const float* x, const float* mask, const float* table, const float* w, int64_t n, double per_level_scale,
                               int base_res, const float* bbox, const float* omin, const float* omax, float in_grad_scale, int enc_only,
                               const float* g_out, float* d_table, float* d_w, float* d_x, float* genc_scratch, void* stream) {
-    if (n < 0 || !bbox) return D3H_ERR_ARG;
+    if (n < 0 || n >= ((int64_t)1 << 36) || !bbox) return D3H_ERR_ARG;
     if (n == 0) return D3H_OK;
     GridCfg g = make_cfg(per_level_scale, base_res);
     TexParams tp = make_tp(bbox, omin, omax, in_grad_scale);
@@ -1075,9 +1170,14 @@ extern "C" int d3h_texmlp_bwd(const float* x, const float* mask, const float* ta
         if (tex_h2 < 0) { const char* e = getenv("D3H_TEX_H2"); tex_h2 = (e && e[0] == '0') ? 0 : 1; }
         // (512-thread workgroups, one per CU -- 251: prime, see above -- each wave a 64-pixel tile at a time)
         const int64_t nwt8 = (n + 511) / 512;
-        if (tex_h2) hipLaunchKernelGGL(texmlp_bwd_mlp_h2_kernel, dim3((unsigned)(nwt8 < 251 ? nwt8 : 251)), dim3(512), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch);
+        // d_x from the MLP half (the h2 kernel only).  D3H_TEX_DX_FUSED=0 (read per call): the encoding half gathers the table again for it, A/B
+        const char* ef = getenv("D3H_TEX_DX_FUSED");
+        float* d_x_mlp = (tex_h2 && !(ef && ef[0] == '0')) ? d_x : nullptr;
+        if (tex_h2 && d_x_mlp) hipLaunchKernelGGL((texmlp_bwd_mlp_h2_kernel<true>), dim3((unsigned)(nwt8 < 251 ? nwt8 : 251)), dim3(512), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch, d_x_mlp);
+        else if (tex_h2) hipLaunchKernelGGL((texmlp_bwd_mlp_h2_kernel<false>), dim3((unsigned)(nwt8 < 251 ? nwt8 : 251)), dim3(512), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch, nof);
         else hipLaunchKernelGGL(texmlp_bwd_mlp_kernel, dim3(gridm), dim3(256), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch);
         d3h_ktime_end(ktm, s);
+        if (d_x_mlp) d_x = nullptr;
         if (d_table || d_x) {
             const int kte = d3h_ktime_begin(D3H_KT_TEX_BWD_ENC, n, s);
             hipLaunchKernelGGL((texmlp_bwd_kernel<1>), dim3(grid2), dim3(256), 0, s, g, tp, x, mask, table, w, n, (const float*)genc_scratch, d_table, nof, d_x,

@@ -25,6 +25,7 @@ def _f6(v):
 
 
 ASYNC_TABLE_GRAD = os.environ.get('D3H_ASYNC_TABLE_GRAD', '1') != '0'      # table-gradient scatter of the backward on its own stream (see _TexMLPFn.backward)
+DX_FUSED = os.environ.get('D3H_TEX_DX_FUSED', '1') != '0'      # position gradient from the MLP half; 0: the three-call sequence (A/B)
 _SIDE = {}
 _PENDING = []
 # One backward pass may hold several nodes that contribute to the SAME table (shade() samples twice for kd_grad / ks_grad, the split
@@ -128,8 +129,12 @@ class _TexMLPFn(torch.autograd.Function):
             # the stream when it ends (queue_callback), a second contribution to the same table joins it first.
             main = _cur_stream()
             _join_scatter()
-            L.check(lib.d3h_texmlp_bwd(*args(), L.i32(0), L.ptr(gc), None, L.ptr(d_w), None, L.ptr(genc), L.stream()), 'texmlp_bwd_mlp')
-            L.check(lib.d3h_texmlp_bwd(*args(), L.i32(1), L.ptr(genc), None, None, L.ptr(d_x), None, L.stream()), 'texmlp_bwd_dx')
+            if DX_FUSED:
+                # (the MLP half writes d_x itself: csrc/texmlp.hip, texmlp_bwd_mlp_h2_kernel)
+                L.check(lib.d3h_texmlp_bwd(*args(), L.i32(0), L.ptr(gc), None, L.ptr(d_w), L.ptr(d_x), L.ptr(genc), L.stream()), 'texmlp_bwd_mlp_dx')
+            else:
+                L.check(lib.d3h_texmlp_bwd(*args(), L.i32(0), L.ptr(gc), None, L.ptr(d_w), None, L.ptr(genc), L.stream()), 'texmlp_bwd_mlp')
+                L.check(lib.d3h_texmlp_bwd(*args(), L.i32(1), L.ptr(genc), None, None, L.ptr(d_x), None, L.stream()), 'texmlp_bwd_dx')
             side.wait_stream(main)
             with L.use_stream(side):
                 L.check(lib.d3h_texmlp_bwd(*args(), L.i32(1), L.ptr(genc), L.ptr(d_tab), None, None, None, L.stream()), 'texmlp_bwd_table')
