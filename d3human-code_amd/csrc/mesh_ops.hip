@@ -189,6 +189,90 @@ __global__ __launch_bounds__(256) void mesh_sdf_kernel(const float* __restrict__
     if (i < np) out[i] = (fabsf(wind) > 6.2831853f ? -1.0f : 1.0f) * sqrtf(best);
 }
 
+// ---- winding-signed distance to an OPEN (or closed) triangle mesh --------------------------------------------------------------
+// The stage hand-off's distance oracle (script/process_body_cloth_head_msdfcut.py:613-747 makes the garment watertight with screened
+// Poisson and asks pysdf): the same loop as mesh_sdf_kernel, with the winding number itself as a second output.  w = solid-angle sum
+// / 4 pi, in turns; sdf = (|w| > 0.5 ? -1 : +1) * distance to the nearest triangle, the test made on the radian sum exactly as
+// mesh_sdf_kernel makes it, so that a closed mesh gives mesh_sdf's bits (a query within rounding of an edge or a vertex of the mesh excepted, where
+// the triangles it lies on are evaluated in float64, see the loop, and mesh_sdf's float32 residue may put the sign of a zero distance either way).  For an open, consistently wound mesh the |w| = 0.5 surface closes the holes.
+// Either output may be NULL.
+// 2 atan2(det, den) of van Oosterom-Strackee for one triangle, in float64 from the float32 vertices
+__device__ float wsdf_angle_f64(V3 p, const float* __restrict__ v, const int* __restrict__ ff) {
+    double r[3][3], l[3];
+    for (int k = 0; k < 3; ++k) {
+        const float* q = v + 3 * (size_t)ff[k];
+        r[k][0] = (double)q[0] - (double)p.x, r[k][1] = (double)q[1] - (double)p.y, r[k][2] = (double)q[2] - (double)p.z;
+        l[k] = sqrt(r[k][0] * r[k][0] + r[k][1] * r[k][1] + r[k][2] * r[k][2]);
+    }
+    const double cx = r[1][1] * r[2][2] - r[1][2] * r[2][1], cy = r[1][2] * r[2][0] - r[1][0] * r[2][2], cz = r[1][0] * r[2][1] - r[1][1] * r[2][0];
+    const double det = r[0][0] * cx + r[0][1] * cy + r[0][2] * cz;
+    const double d01 = r[0][0] * r[1][0] + r[0][1] * r[1][1] + r[0][2] * r[1][2], d02 = r[0][0] * r[2][0] + r[0][1] * r[2][1] + r[0][2] * r[2][2];
+    const double d12 = r[1][0] * r[2][0] + r[1][1] * r[2][1] + r[1][2] * r[2][2];
+    return (float)(2.0 * atan2(det, l[0] * l[1] * l[2] + d01 * l[2] + d02 * l[1] + d12 * l[0]));
+}
+
+__global__ __launch_bounds__(256) void mesh_wsdf_kernel(const float* __restrict__ pts, int np, const float* __restrict__ v, const int* __restrict__ f,
+                                                        int nf, float* __restrict__ out_sdf, float* __restrict__ out_w) {
+    __shared__ float tri[MSDF_TILE * 9];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    V3 p = mk(0.f, 0.f, 0.f);
+    if (i < np) p = ld3(pts + 3 * (size_t)i);
+    float best = INFINITY, wind = 0.f, fix = 0.f;
+    for (int base = 0; base < nf; base += MSDF_TILE) {
+        const int cnt = min(MSDF_TILE, nf - base);
+        __syncthreads();
+        for (int t = threadIdx.x; t < cnt; t += 256) {
+            const int* ff = f + 3 * (size_t)(base + t);
+            V3 a = ld3(v + 3 * (size_t)ff[0]), b = ld3(v + 3 * (size_t)ff[1]), c = ld3(v + 3 * (size_t)ff[2]);
+            st3(tri + 9 * t, a); st3(tri + 9 * t + 3, b - a); st3(tri + 9 * t + 6, c - a);
+        }
+        __syncthreads();
+        for (int t = 0; t < cnt; ++t) {
+            V3 a = ld3(tri + 9 * t), ab = ld3(tri + 9 * t + 3), ac = ld3(tri + 9 * t + 6);
+            best = fminf(best, tri_dist2(p, a, ab, ac));
+            V3 ra = a - p, rb = ra + ab, rc = ra + ac;
+            float la = sqrtf(dot(ra, ra)), lb = sqrtf(dot(rb, rb)), lc = sqrtf(dot(rc, rc));
+            float det = dot(ra, cross(rb, rc));
+            float den = la * lb * lc + dot(ra, rb) * lc + dot(ra, rc) * lb + dot(rb, rc) * la;
+            // A query within rounding of the triangle's plane (a point ON the mesh: a vertex of it, a point of an edge): det, and on an edge den too, are
+            // rounding residue in float32, and the residue would decide between 0 and +-half a turn.  That triangle alone is evaluated in float64 from
+            // the vertices themselves (the staged edges are already rounded); everything else stays mesh_sdf_kernel's arithmetic.
+            // `wind` itself is mesh_sdf_kernel's sum, untouched; `fix` collects what the repaired triangles change.
+            const float ang = 2.0f * atan2f(det, den);
+            wind += ang;
+            if (fabsf(det) < 1e-4f * (la * lb * lc)) fix += wsdf_angle_f64(p, v, f + 3 * (size_t)(base + t)) - ang;
+        }
+    }
+    if (i >= np) return;
+    // Within 1e-3 rad of the decision itself (a query ON a face of a closed mesh: half a turn exactly) either side is right: mesh_sdf_kernel's is taken.
+    const float rep = wind + fix;
+    const bool inside = fabsf(fabsf(rep) - 6.2831853f) < 1e-3f ? fabsf(wind) > 6.2831853f : fabsf(rep) > 6.2831853f;
+    if (out_sdf) out_sdf[i] = (inside ? -1.0f : 1.0f) * sqrtf(best);
+    if (out_w) out_w[i] = rep * 0.079577472f;                                           // 1 / (4 pi)
+}
+
+// ---- collision push: one Jacobi round of deform_body_collision (script/process_body_cloth_head_msdfcut.py:337-347) ---------------
+// v[i] -= n[i] / (|n[i]| + 1e-7) * eps wherever sdf_in[i] < margin (sdf_in positive INSIDE, pysdf's sign, taken by the caller before the
+// round).  A vertex whose normal has length 0 (one that no face uses) would be displaced by nothing: it is left alone and not counted, so that it cannot
+// keep the caller's rounds going.  moved[0] += the number of vertices pushed (one atomic per wave); pushes[i] += 1 for each of them (optional).
+__global__ __launch_bounds__(256) void collision_push_kernel(float* __restrict__ v, const float* __restrict__ n, const float* __restrict__ sdf_in, int nv,
+                                                             float margin, float eps, int* __restrict__ moved, int* __restrict__ pushes) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool push = i < nv && sdf_in[i] < margin;
+    V3 nn = mk(0.f, 0.f, 0.f);
+    if (push) {
+        nn = ld3(n + 3 * (size_t)i);
+        push = dot(nn, nn) > 0.f;
+    }
+    if (push) {
+        V3 u = nn * (1.0f / (sqrtf(dot(nn, nn)) + 1e-7f));
+        st3(v + 3 * (size_t)i, ld3(v + 3 * (size_t)i) - u * eps);
+        if (pushes) pushes[i] += 1;
+    }
+    const unsigned long long b = __ballot(push);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(moved, (int)__popcll(b));
+}
+
 inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
@@ -267,6 +351,26 @@ extern "C" int d3h_collision_bwd(const float* cloth, int nc, const float* body, 
 extern "C" int d3h_mesh_sdf(const float* pts, int np, const float* v, const int* f, int nf, float* out, void* stream) {
     if (np < 0 || nf <= 0 || (np > 0 && (!pts || !v || !f || !out))) return D3H_ERR_ARG;
     if (np > 0) hipLaunchKernelGGL(mesh_sdf_kernel, grid256(np), dim3(256), 0, (hipStream_t)stream, pts, np, v, f, nf, out);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// out_sdf[np] (may be NULL): (|w| > 0.5 ? -1 : +1) * distance of pts[np][3] to the nearest triangle of the mesh (v, f int32 [nf][3]), which may be
+// open; out_w[np] (may be NULL): the generalised winding number in turns.  A closed mesh gives out_sdf == d3h_mesh_sdf's out, bit for bit (but for the sign
+// of a zero distance at a query on the mesh's own edges: the triangles a query lies on are evaluated in float64).
+extern "C" int d3h_mesh_wsdf(const float* pts, int np, const float* v, const int* f, int nf, float* out_sdf, float* out_w, void* stream) {
+    if (np < 0 || nf <= 0 || (np > 0 && (!pts || !v || !f))) return D3H_ERR_ARG;
+    if (np > 0 && (out_sdf || out_w)) hipLaunchKernelGGL(mesh_wsdf_kernel, grid256(np), dim3(256), 0, (hipStream_t)stream, pts, np, v, f, nf, out_sdf, out_w);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// one round of the hand-off's collision push: v[nv][3] updated in place, v[i] -= n[i] / (|n[i]| + 1e-7) * eps where sdf_in[i] < margin (sdf_in[nv]
+// positive inside) and n[i] is not the zero vector; moved[1] int32 accumulated with the number of vertices pushed; pushes[nv] int32 (may be NULL) += 1 for
+// each of them
+extern "C" int d3h_collision_push(float* v, const float* n, const float* sdf_in, int nv, float margin, float eps, int* moved, int* pushes, void* stream) {
+    if (nv < 0 || !moved || (nv > 0 && (!v || !n || !sdf_in))) return D3H_ERR_ARG;
+    if (nv > 0) hipLaunchKernelGGL(collision_push_kernel, grid256(nv), dim3(256), 0, (hipStream_t)stream, v, n, sdf_in, nv, margin, eps, moved, pushes);
     D3H_LAUNCH_CHECK();
     return D3H_OK;
 }

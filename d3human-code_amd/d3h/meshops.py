@@ -163,3 +163,42 @@ def mesh_sdf(points, verts, faces):
     out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
     L.check(L.lib().d3h_mesh_sdf(L.ptr(p), L.i32(p.shape[0]), L.ptr(v), L.ptr(f.contiguous()), L.i32(f.shape[0]), L.ptr(out), L.stream()), 'mesh_sdf')
     return out
+
+
+def mesh_wsdf(points, verts, faces, want_sdf=True, want_w=True, check=True):
+    """-> (sdf, w) of points [n,3] against the triangle mesh (verts [V,3], faces [F,3], F > 0), which may be OPEN: w is the generalised winding
+    number in turns (solid-angle sum / 4 pi), sdf = (|w| > 0.5 ? -1 : +1) * distance to the nearest triangle.  A triangle whose plane the query lies in
+    to within rounding (a query ON the mesh) is evaluated in float64, so that w does not hang on float32 residue there.  On a closed mesh sdf is
+    mesh_sdf, bit for bit; on an open, consistently wound one the |w| = 0.5 surface closes the holes.  An output that is not wanted is None.
+    check=False skips the range check of the faces (two read-backs) for a caller that has made it, such as a field queried every round."""
+    p = points.detach().contiguous().float()
+    v = verts.detach().contiguous().float()
+    if p.dim() != 2 or p.shape[1] != 3 or v.dim() != 2 or v.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError(f'mesh_wsdf: expected points [n,3], verts [V,3], faces [F,3], got {tuple(p.shape)} {tuple(v.shape)} {tuple(faces.shape)}')
+    f = (faces if faces.dtype == torch.int32 else faces.int()).contiguous()
+    if check and f.shape[0] > 0 and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
+        raise RuntimeError('mesh_wsdf: a face index outside [0, V)')
+    sdf = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if want_sdf else None
+    w = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if want_w else None
+    L.check(L.lib().d3h_mesh_wsdf(L.ptr(p), L.i32(p.shape[0]), L.ptr(v), L.ptr(f), L.i32(f.shape[0]), L.ptr(sdf), L.ptr(w), L.stream()), 'mesh_wsdf')
+    return sdf, w
+
+
+def collision_push(v, normals, field, eps=0.005, margin=0.002, rounds=100, stop_when_still=True):
+    """the reference's deform_body_collision (script/process_body_cloth_head_msdfcut.py:331-349) as Jacobi rounds on the device: each round takes
+    sdf_in = field(v) once (positive INSIDE, pysdf's sign; `field` maps a float32 [n,3] device tensor to [n]), then v[i] -= n[i] / (|n[i]| + 1e-7) * eps
+    wherever sdf_in[i] < margin and n[i] is not zero (a zero normal would move the vertex by nothing).  Stops when a round moves nothing (one count read-back per round) or after `rounds`.
+    -> (v', pushes int32 [n]: how often each vertex moved)"""
+    x = v.detach().clone().contiguous().float()
+    nrm = normals.detach().contiguous().float()
+    n = x.shape[0]
+    pushes = torch.zeros(n, dtype=torch.int32, device=x.device)
+    moved = torch.zeros(1, dtype=torch.int32, device=x.device)
+    for _ in range(int(rounds)):
+        s = field(x).contiguous().float()
+        moved.zero_()
+        L.check(L.lib().d3h_collision_push(L.ptr(x), L.ptr(nrm), L.ptr(s), L.i32(n), L.f32(margin), L.f32(eps), L.ptr(moved), L.ptr(pushes), L.stream()),
+                'collision_push')
+        if stop_when_still and int(moved.item()) == 0:
+            break
+    return x, pushes

@@ -1327,10 +1327,73 @@ def gen_close_hole():
     print('close_hole.npz:', os.path.getsize(os.path.join(GOLD, 'close_hole.npz')), 'bytes')
 
 
+def gen_msdfcut():
+    """reference script/process_body_cloth_head_msdfcut.py on the CPU: its own deform_body_collision (:331-349), find_inside_point (:373-388),
+    merge_meshes_with_face_labels (:351-371) and face_in_bbox (:391-401) on the small seeded inputs tests/handoff_cases.py generates, with an analytic
+    sphere sdf_gt_fn(x) = 0.5 - |x| in place of pysdf.  openmesh, open3d, pymeshlab and pysdf are stubbed (a TriangleMesh that holds vertices and
+    triangles); scipy's KDTree is the real one.  Only inputs and outputs are recorded."""
+    import tempfile
+    refharness.install()
+
+    class TriangleMesh:
+        def __init__(self, v=None, f=None):
+            self.vertices = np.zeros((0, 3)) if v is None else np.array(v, np.float64)
+            self.triangles = np.zeros((0, 3), np.int64) if f is None else np.array(f, np.int64)
+
+        def compute_vertex_normals(self):
+            return self
+
+    refharness.stub('openmesh')
+    refharness.stub('open3d')
+    refharness.stub('open3d.geometry', TriangleMesh=TriangleMesh)
+    refharness.stub('open3d.utility', Vector3dVector=lambda a: np.array(a, np.float64), Vector3iVector=lambda a: np.array(a, np.int64))
+    refharness.stub('open3d.io')
+    refharness.stub('pymeshlab')
+    refharness.stub('pysdf')
+    import script.process_body_cloth_head_msdfcut as rcut
+    assert rcut.__file__.startswith(refharness.REF)
+    sys.path.append(os.path.join(ROOT, 'd3human-code_amd'))        # AFTER the reference: the cases module imports d3h (it only generates inputs here)
+    sys.path.append(os.path.join(ROOT, 'tests'))
+    import handoff_cases as HC
+    sphere = lambda x: 0.5 - np.linalg.norm(np.asarray(x, np.float64), axis=1)
+    out = {}
+    # the push: 300 vertices with radial normals; no vertex ever comes within 5e-4 of the decision boundary (sdf_gt_fn = 0.002), asserted on the
+    # reference's own trajectory by wrapping the callable
+    pv, pn, _ = HC.push_inputs()
+    closest = [np.inf]
+
+    def watched(x):
+        s = sphere(x)
+        closest[0] = min(closest[0], float(np.abs(s - 0.002).min()))
+        return s
+    cloth = np.random.default_rng(31).normal(size=(50, 3))          # deform_body_collision builds a kd-tree of it and drops the answers
+    pushed = rcut.deform_body_collision(cloth, None, pv.astype(np.float64), pn.astype(np.float64), watched)
+    assert closest[0] >= 5e-4, closest[0]
+    out.update({'push.v': pv, 'push.n': pn, 'push.out': pushed})
+    print(f'msdfcut push: {len(pv)} vertices, closest approach to the decision boundary {closest[0]:.2e}, moved at most '
+          f'{np.linalg.norm(pushed - pv, axis=1).max():.4f}')
+    # find_inside_point
+    pts, body_index = HC.inside_inputs()
+    with tempfile.TemporaryDirectory() as d:
+        ins, outs = rcut.find_inside_point(pts, body_index, sphere, d)
+    assert np.abs(sphere(pts[body_index]) + 0.002).min() >= 5e-4
+    out.update({'inside.v': pts, 'inside.body_index': body_index, 'inside.inside': np.asarray(ins), 'inside.outside': np.asarray(outs)})
+    # merge_meshes_with_face_labels (the reference shifts mesh2's triangles in place: it gets a copy) and face_in_bbox
+    (v1, f1), (v2, f2), v_indices = HC.label_inputs()
+    _, labels, mv, mf = rcut.merge_meshes_with_face_labels(TriangleMesh(v1, f1), TriangleMesh(v2, f2.copy()))
+    out.update({'labels.v1': v1, 'labels.f1': f1, 'labels.v2': v2, 'labels.f2': f2, 'labels.labels': np.asarray(labels), 'labels.v': np.asarray(mv),
+                'labels.f': np.asarray(mf)})
+    fin, fout = rcut.face_in_bbox(v_indices, f1)
+    out.update({'bbox.v_indices': v_indices, 'bbox.in': np.asarray(fin, np.int64).reshape(-1, 3), 'bbox.out': np.asarray(fout, np.int64).reshape(-1, 3)})
+    print(f'msdfcut: inside {len(ins)} / outside {len(outs)}; labels {np.bincount(labels).tolist()}; faces in the box {len(fin)} of {len(f1)}')
+    _savez_reproducible(os.path.join(GOLD, 'msdfcut.npz'), npy(out))
+    print('msdfcut.npz:', os.path.getsize(os.path.join(GOLD, 'msdfcut.npz')), 'bytes')
+
+
 # dependency order: imgops / render read mtets_gshell_n8.npz, tick_split / tick_seq read tick_init.npz, tick_seq reads seq.npz (from GOLD)
 ALL = {'sdf_mlp': gen_sdf_mlp, 'mtets': gen_mtets, 'lbs': gen_lbs, 'imgops': gen_imgops, 'render': gen_render, 'seq': gen_seq, 'lpips': gen_lpips,
        'data_edges': gen_data_edges, 'tick_init': gen_tick_init, 'tick_split': gen_tick_split, 'tick_seq': gen_tick_seq,
-       'texture2d': gen_texture2d, 'close_hole': gen_close_hole}
+       'texture2d': gen_texture2d, 'close_hole': gen_close_hole, 'msdfcut': gen_msdfcut}
 
 if __name__ == '__main__':
     names = sys.argv[1:] or list(ALL)
