@@ -47,9 +47,7 @@ class _BsdfFn(torch.autograd.Function):
         B, H, W = shp
         n = len(keep)
         out = torch.empty(B, H, W, cout, dtype=torch.float32, device=keep[0].device)
-        P = ctypes.c_void_p * n
-        L.check(L.lib().d3h_bsdf_fwd(L.i32(op), L.i32(n), P(*[L.ptr(t).value for t in keep]), strides, L.i32(B), L.i32(H), L.i32(W),
-                                     ctypes.c_double(min_roughness), L.i32(frostbite), L.ptr(out), L.stream()), name + '_fwd')
+        L.call('bsdf_fwd', op, n, L.ptr_array(keep), strides, B, H, W, min_roughness, frostbite, out)
         ctx.save_for_backward(*keep)
         ctx.meta = (op, float(min_roughness), int(frostbite), shp, [tuple(t.shape) for t in ins])
         return out
@@ -66,10 +64,8 @@ class _BsdfFn(torch.autograd.Function):
         red = [int(H * W > 1 and t.shape[1] == 1 and t.shape[2] == 1) for t in keep]
         grads = [None if not ctx.needs_input_grad[3 + k] else L.zeros((keep[k].shape[0], 1, 1, c), torch.float32, g.device) if red[k]
                  else torch.empty(B, H, W, c, dtype=torch.float32, device=g.device) for k, c in enumerate(cin)]
-        P = ctypes.c_void_p * n
-        L.check(L.lib().d3h_bsdf_bwd(L.i32(op), L.i32(n), P(*[L.ptr(t).value for t in keep]), strides, L.i32(B), L.i32(H), L.i32(W),
-                                     ctypes.c_double(min_roughness), L.i32(frostbite), L.ptr(g.contiguous().float()),
-                                     P(*[None if d is None else L.ptr(d).value for d in grads]), (ctypes.c_int * n)(*red), L.stream()), name + '_bwd')
+        L.call('bsdf_bwd', op, n, L.ptr_array(keep), strides, B, H, W, min_roughness, frostbite, g.contiguous().float(), L.ptr_array(grads),
+               (ctypes.c_int * n)(*red))
         outs = []
         for gr, shape in zip(grads, in_shapes):
             if gr is not None:

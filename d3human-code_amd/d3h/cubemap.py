@@ -46,7 +46,7 @@ def texel_table(N, device):
     t = _TABLES.get(key)
     if t is None:
         table = torch.empty(6 * N * N, 4, dtype=torch.float32, device=device)
-        L.check(L.lib().d3h_cubemap_table(L.i32(N), L.ptr(table), L.stream()), 'cubemap_table')
+        L.call('cubemap_table', N, table)
         t = _TABLES[key] = (table, torch.from_numpy(patch_cones(N)).float().to(device).contiguous())
     return t
 
@@ -75,7 +75,7 @@ class _DiffuseFn(torch.autograd.Function):
         N = _check(cubemap, 'diffuse_cubemap')
         c = cubemap.contiguous().float()
         out = torch.empty_like(c)
-        L.check(L.lib().d3h_cubemap_diffuse(*[L.ptr(t) for t in texel_table(N, c.device)], L.ptr(c), L.i32(N), L.i32(0), L.ptr(out), L.stream()), 'cubemap_diffuse_fwd')
+        L.call('cubemap_diffuse', *texel_table(N, c.device), c, N, 0, out)
         ctx.N = N
         return out
 
@@ -83,7 +83,7 @@ class _DiffuseFn(torch.autograd.Function):
     def backward(ctx, g):
         g = g.contiguous().float()
         d = torch.empty_like(g)
-        L.check(L.lib().d3h_cubemap_diffuse(*[L.ptr(t) for t in texel_table(ctx.N, g.device)], L.ptr(g), L.i32(ctx.N), L.i32(1), L.ptr(d), L.stream()), 'cubemap_diffuse_bwd')
+        L.call('cubemap_diffuse', *texel_table(ctx.N, g.device), g, ctx.N, 1, d)
         return d
 
 
@@ -94,8 +94,7 @@ class _SpecularFn(torch.autograd.Function):
         c = cubemap.contiguous().float()
         out = torch.empty_like(c)
         wsum = torch.empty(6 * N * N, dtype=torch.float32, device=c.device)
-        L.check(L.lib().d3h_cubemap_specular_fwd(*[L.ptr(t) for t in texel_table(N, c.device)], L.ptr(c), L.i32(N), L.f32(roughness), L.f32(cut), L.ptr(out), L.ptr(wsum),
-                                                 L.stream()), 'cubemap_specular_fwd')
+        L.call('cubemap_specular_fwd', *texel_table(N, c.device), c, N, roughness, cut, out, wsum)
         ctx.save_for_backward(wsum)            # depends on (N, roughness, cutoff) only, not on the cubemap
         ctx.meta = (N, float(roughness), float(cut))
         return out
@@ -106,8 +105,7 @@ class _SpecularFn(torch.autograd.Function):
         N, roughness, cut = ctx.meta
         g = g.contiguous().float()
         d = torch.empty_like(g)
-        L.check(L.lib().d3h_cubemap_specular_bwd(*[L.ptr(t) for t in texel_table(N, g.device)], L.ptr(g), L.ptr(wsum), L.i32(N), L.f32(roughness), L.f32(cut), L.ptr(d),
-                                                 L.stream()), 'cubemap_specular_bwd')
+        L.call('cubemap_specular_bwd', *texel_table(N, g.device), g, wsum, N, roughness, cut, d)
         return d, None, None
 
 

@@ -13,10 +13,6 @@ EMB = 51
 HIDDEN_KEYS = (2, 4, 6, 10, 12)
 
 
-def _lib():
-    return L.lib()
-
-
 def supported(net):
     """True when `net` (geometry.mlp.MLP_deform) has the shape the kernels are built for"""
     want = {0: (256, CODE + EMB), 2: (256, 256), 4: (256, 256), 6: (256, 256), 8: (256, 256 + EMB), 10: (256, 256), 12: (256, 256), 14: (3, 256)}
@@ -29,7 +25,6 @@ def supported(net):
 class _DeformMLPFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, code, *params):
-        lib = _lib()
         w = {i: params[2 * k] for k, i in enumerate((0, 2, 4, 6, 8, 10, 12, 14))}
         b = {i: params[2 * k + 1] for k, i in enumerate((0, 2, 4, 6, 8, 10, 12, 14))}
         c = code.reshape(CODE).float()
@@ -42,13 +37,12 @@ class _DeformMLPFn(torch.autograd.Function):
         w7, b7 = w[14].detach().contiguous().float(), b[14].detach().contiguous().float()
         xc = x.detach().reshape(-1, 3).contiguous().float()
         n, dev = xc.shape[0], xc.device
-        wp = torch.empty(lib.d3h_deform_mlp_wpack_floats(), dtype=torch.float32, device=dev)
-        L.check(lib.d3h_deform_mlp_pack(L.ptr(w0e), L.ptr(b0f), L.ptr(wh), L.ptr(bh), L.ptr(w4), L.ptr(b4), L.ptr(w7), L.ptr(b7), L.ptr(wp), L.stream()),
-                'deform_mlp_pack')
+        wp = torch.empty(L.query('deform_mlp_wpack_floats'), dtype=torch.float32, device=dev)
+        L.call('deform_mlp_pack', w0e, b0f, wh, bh, w4, b4, w7, b7, wp)
         need = code.requires_grad or any(p.requires_grad for p in params)
         out = torch.empty(n, 3, dtype=torch.float32, device=dev)
-        act = torch.empty(lib.d3h_deform_mlp_act_floats(n), dtype=torch.float32, device=dev) if need else None
-        L.check(lib.d3h_deform_mlp_fwd(L.ptr(xc), None, L.f32(0.0), L.ptr(wp), L.ptr(out), None, L.ptr(act), L.i64(n), L.i32(0), L.stream()), 'deform_mlp_fwd')
+        act = torch.empty(L.query('deform_mlp_act_floats', n), dtype=torch.float32, device=dev) if need else None
+        L.call('deform_mlp_fwd', xc, None, 0.0, wp, out, None, act, n, 0)
         if need:
             ctx.save_for_backward(xc, c.detach(), W0, w0e, wh, w4, w7, act)
         ctx.xshape = x.shape
@@ -56,18 +50,15 @@ class _DeformMLPFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib()
         xc, c, W0, w0e, wh, w4, w7, act = ctx.saved_tensors
         n, dev = xc.shape[0], xc.device
-        wpt = torch.empty(lib.d3h_deform_mlp_wpackt_floats(), dtype=torch.float32, device=dev)
-        L.check(lib.d3h_deform_mlp_pack_t(L.ptr(w0e), L.ptr(wh), L.ptr(w4), L.ptr(wpt), L.stream()), 'deform_mlp_pack_t')
+        wpt = torch.empty(L.query('deform_mlp_wpackt_floats'), dtype=torch.float32, device=dev)
+        L.call('deform_mlp_pack_t', w0e, wh, w4, wpt)
         gout = g.reshape(-1, 3).contiguous().float()
         dz = torch.empty_like(act)
         sizes = [256 * EMB, 256, 5 * 65536, 5 * 256, 256 * (256 + EMB), 256, 3 * 256, 3]
         dw0e, db0, dwh, dbh, dw4, db4, dw7, db7 = torch.split(torch.zeros(sum(sizes), dtype=torch.float32, device=dev), sizes)
-        L.check(lib.d3h_deform_mlp_bwd(L.ptr(xc), None, L.f32(0.0), L.ptr(gout), L.ptr(w7), L.ptr(wpt), None, L.ptr(act), L.ptr(dz), L.i64(n), None,
-                                       L.ptr(dw0e), L.ptr(db0), L.ptr(dwh), L.ptr(dbh), L.ptr(dw4), L.ptr(db4), L.ptr(dw7), L.ptr(db7), None,
-                                       None, L.i32(0), L.i32(0), L.i32(0), L.stream()), 'deform_mlp_bwd')
+        L.call('deform_mlp_bwd', xc, None, 0.0, gout, w7, wpt, None, act, dz, n, None, dw0e, db0, dwh, dbh, dw4, db4, dw7, db7, None, None, 0, 0, 0)
         dW0 = torch.cat([torch.outer(db0, c), dw0e.view(256, EMB)], dim=1)            # unfold the pose code from the first bias
         dcode = (W0[:, :CODE].t() @ db0).reshape(1, 1, CODE)
         dwh, dbh = dwh.view(5, 256, 256), dbh.view(5, 256)

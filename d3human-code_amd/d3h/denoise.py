@@ -6,8 +6,6 @@ caller divides.  Only col gets a gradient; the backward is the exact adjoint as 
 bilateral_denoise_many([col_a, col_b], nrm, zdz, sigma) -> the same for one or two images that share the guides (the demodulated path: diffuse and
 specular light), one launch each way: the guide planes are staged and the tap weights computed once.  Each image's output and gradient equal the
 single-image call's bit for bit."""
-import ctypes
-
 import torch
 
 from . import _lib as L
@@ -16,8 +14,7 @@ from . import _lib as L
 def _run(v, nrm, zdz, sigma, backward, channels):
     B, H, W = nrm.shape[:3]
     out = torch.empty(B, H, W, channels, dtype=torch.float32, device=nrm.device)
-    L.check(L.lib().d3h_bilateral_denoise(L.ptr(v), L.ptr(nrm), L.ptr(zdz), L.i32(B), L.i32(H), L.i32(W), L.f32(sigma), L.i32(backward), L.ptr(out),
-                                          L.stream()), 'bilateral_denoise_bwd' if backward else 'bilateral_denoise_fwd')
+    L.call('bilateral_denoise', v, nrm, zdz, B, H, W, sigma, backward, out)
     return out
 
 
@@ -56,10 +53,7 @@ def _check(col, nrm, zdz, sigma):
 def _run_n(vs, nrm, zdz, sigma, backward, channels):
     B, H, W = nrm.shape[:3]
     outs = [torch.empty(B, H, W, channels, dtype=torch.float32, device=nrm.device) for _ in vs]
-    arr = ctypes.c_void_p * len(vs)
-    L.check(L.lib().d3h_bilateral_denoise_n(arr(*[L.ptr(v).value for v in vs]), L.i32(len(vs)), L.ptr(nrm), L.ptr(zdz), L.i32(B), L.i32(H), L.i32(W), L.f32(sigma),
-                                            L.i32(backward), arr(*[L.ptr(o).value for o in outs]), L.stream()),
-            'bilateral_denoise_n_bwd' if backward else 'bilateral_denoise_n_fwd')
+    L.call('bilateral_denoise_n', L.ptr_array(vs), len(vs), nrm, zdz, B, H, W, sigma, backward, L.ptr_array(outs))
     return outs
 
 

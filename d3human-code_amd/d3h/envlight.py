@@ -15,5 +15,5 @@ def tables(base):
     base = base.detach().float().contiguous()
     pdf, cols = (torch.empty(H, W, dtype=torch.float32, device=base.device) for _ in range(2))
     rows, rowtot = (torch.empty(H, dtype=torch.float32, device=base.device) for _ in range(2))
-    L.check(L.lib().d3h_envlight_tables(L.ptr(base), L.i32(H), L.i32(W), L.ptr(pdf), L.ptr(rows), L.ptr(cols), L.ptr(rowtot), L.stream()), 'envlight_tables')
+    L.call('envlight_tables', base, H, W, pdf, rows, cols, rowtot)
     return pdf, rows[:, None].expand(H, W), cols

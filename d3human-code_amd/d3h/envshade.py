@@ -6,8 +6,6 @@ shadow_scale) -> (diff [B,H,W,3], spec [B,H,W,3]).  `bvh` is a d3h.raytrace.Bvh 
 saved but the inputs.  Gradients: gb_pos, gb_normal, gb_kd, gb_ks (plain stores; None for gb_pos, gb_kd, gb_ks in the two Lambert modes, where they
 are zero) and light (float atomics per texel).  Sample directions, pdfs and visibility carry no gradient.  Inputs of any stride are made float32
 and contiguous here (the reference passes rast[..., -1] as mask and lgt.rows[:, 0] as rows)."""
-import ctypes
-
 import torch
 
 from . import _lib as L
@@ -30,9 +28,8 @@ def _prep(bvh, mask, gb, light, pdf, rows, cols, perms, n):
     perms = perms.detach().contiguous()
     if perms.dtype != torch.int32 or perms.dim() != 2 or perms.shape[0] < 1 or perms.shape[1] != n * n:
         raise RuntimeError(f'env_shade: perms must be int32 [R >= 1, {n * n}], got {perms.dtype} {tuple(perms.shape)}')
-    P = ctypes.c_void_p * 7
-    head = [L.ptr(bvh.nodes), L.ptr(bvh.tri9), L.i64(bvh.F), P(*[L.ptr(t).value for t in gbuf]), L.ptr(light), L.i32(light.shape[0]), L.i32(light.shape[1]),
-            L.ptr(pdf), L.ptr(rows), L.ptr(cols), L.i32(pdf.shape[0]), L.i32(pdf.shape[1]), L.ptr(perms), L.i32(perms.shape[0]), L.i64(B * H * W)]
+    head = [bvh.nodes, bvh.tri9, bvh.F, L.ptr_array(gbuf), light, light.shape[0], light.shape[1], pdf, rows, cols, pdf.shape[0], pdf.shape[1], perms,
+            perms.shape[0], B * H * W]
     return (B, H, W), light, head
 
 
@@ -43,8 +40,7 @@ class _EnvShadeFn(torch.autograd.Function):
         dev = gb_pos.device
         diff = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
         spec = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev)
-        L.check(L.lib().d3h_env_shade_fwd(*head, L.i32(BSDF), L.i32(n), ctypes.c_uint(seed & 0xffffffff), L.f32(shadow_scale), L.ptr(diff), L.ptr(spec),
-                                          L.stream()), 'env_shade_fwd')
+        L.call('env_shade_fwd', *head, BSDF, n, seed & 0xffffffff, shadow_scale, diff, spec)
         ctx.save_for_backward(mask, ro, gb_pos, gb_normal, gb_view_pos, gb_kd, gb_ks, light, pdf, rows, cols, perms)
         ctx.meta = (bvh, int(BSDF), int(n), int(bwd_seed), float(shadow_scale))
         return diff, spec
@@ -59,9 +55,8 @@ class _EnvShadeFn(torch.autograd.Function):
         d_nrm = new()
         d_pos, d_kd, d_ks = (new(), new(), new()) if BSDF == 0 else (None, None, None)
         d_light = L.zeros(tuple(light_c.shape), torch.float32, dev)
-        L.check(L.lib().d3h_env_shade_bwd(*head, L.i32(BSDF), L.i32(n), ctypes.c_uint(seed & 0xffffffff), L.f32(shadow_scale),
-                                          L.ptr(g_diff.contiguous().float()), L.ptr(g_spec.contiguous().float()), L.ptr(d_pos), L.ptr(d_nrm), L.ptr(d_kd),
-                                          L.ptr(d_ks), L.ptr(d_light), L.stream()), 'env_shade_bwd')
+        L.call('env_shade_bwd', *head, BSDF, n, seed & 0xffffffff, shadow_scale, g_diff.contiguous().float(), g_spec.contiguous().float(), d_pos,
+               d_nrm, d_kd, d_ks, d_light)
         fit = lambda d, t: None if d is None else d.reshape(t.shape)
         return (None, None, None, fit(d_pos, gb_pos), fit(d_nrm, gb_normal), None, fit(d_kd, gb_kd), fit(d_ks, gb_ks), d_light.reshape(light.shape),
                 None, None, None, None, None, None, None, None, None)

@@ -26,7 +26,6 @@ The contract.  `n_input_dims` 1..256 -> `n_hidden_layers` (1..8) hidden layers o
 `output_activation` "None", `n_neurons` 128, `n_hidden_layers` 5.  NotImplementedError (naming the key): other otypes, other activations
 ("Sine", "Squareplus"), other widths.  ValueError: a non-positive or out-of-range `n_hidden_layers`, `n_input_dims`, `n_output_dims`.
 """
-import ctypes
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -79,16 +78,12 @@ class MLPConfig:
         self.n_params = sum(a * b for a, b in self.shapes)
 
     def _kernel_args(self):
-        return (L.i32(self.n_input_dims), L.i32(self.n_neurons), L.i32(self.n_hidden_layers), L.i32(self.n_output_dims),
-                L.i32(ACTIVATIONS[self.activation]), L.i32(ACTIVATIONS[self.output_activation]))
+        return (self.n_input_dims, self.n_neurons, self.n_hidden_layers, self.n_output_dims, ACTIVATIONS[self.activation],
+                ACTIVATIONS[self.output_activation])
 
     def __repr__(self):
         return (f'MLPConfig({self.n_input_dims} -> {self.n_neurons} x {self.n_hidden_layers} -> {self.n_output_dims}, {self.activation}, '
                 f'output {self.output_activation}: {self.n_params} parameters)')
-
-
-def _ptr_array(ts):
-    return (ctypes.c_void_p * len(ts))(*[None if t is None else L.ptr(t).value for t in ts])
 
 
 def _vec(v, n, dev, what):
@@ -121,8 +116,7 @@ class _FusedMLPFn(torch.autograd.Function):
         sc, bi = _vec(out_scale, cfg.n_output_dims, dev, 'out_scale'), _vec(out_bias, cfg.n_output_dims, dev, 'out_bias')
         out = torch.empty(n, cfg.n_output_dims, dtype=torch.float32, device=dev)
         if n > 0:
-            L.check(L.lib().d3h_fusedmlp_fwd(L.ptr(xs), L.i64(n), *cfg._kernel_args(), _ptr_array(ws), L.ptr(mk), L.ptr(sc), L.ptr(bi),
-                                             L.ptr(out), L.i32(max_cus), L.stream()), 'fusedmlp_fwd')
+            L.call('fusedmlp_fwd', xs, n, *cfg._kernel_args(), L.ptr_array(ws), mk, sc, bi, out, max_cus)
         ctx.save_for_backward(xs, *ws)                     # inputs only: no activation is kept
         ctx.cfg, ctx.mask, ctx.scale, ctx.xshape, ctx.in_grad_scale, ctx.max_cus = cfg, mk, sc, x.shape, float(in_grad_scale), int(max_cus)
         return out
@@ -137,9 +131,8 @@ class _FusedMLPFn(torch.autograd.Function):
         d_w = [L.zeros_like(w) if nw else None for w, nw in zip(ws, need_w)]
         if n > 0 and (d_x is not None or any(need_w)):
             gc = g.reshape(n, cfg.n_output_dims).contiguous().float()
-            L.check(L.lib().d3h_fusedmlp_bwd(L.ptr(xs), L.i64(n), *cfg._kernel_args(), _ptr_array(ws), L.ptr(ctx.mask), L.ptr(ctx.scale),
-                                             L.ptr(gc), L.f32(ctx.in_grad_scale), L.ptr(d_x), _ptr_array(d_w) if any(need_w) else None,
-                                             L.i32(ctx.max_cus), L.stream()), 'fusedmlp_bwd')
+            L.call('fusedmlp_bwd', xs, n, *cfg._kernel_args(), L.ptr_array(ws), ctx.mask, ctx.scale, gc, ctx.in_grad_scale, d_x,
+                   L.ptr_array(d_w) if any(need_w) else None, ctx.max_cus)
         return (d_x.reshape(ctx.xshape) if d_x is not None else None, None, None, None, None, None, None) + tuple(d_w)
 
 

@@ -83,22 +83,23 @@ class GridConfig:
         n = self.n_levels
         scale, res, hashed = (ctypes.c_float * n)(), (ctypes.c_int * n)(), (ctypes.c_int * n)()
         offset, size, total = (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)(), ctypes.c_int64(0)
-        rc = L.lib().d3h_gridenc_layout(*self._cfg_args(), scale, res, offset, size, hashed, ctypes.byref(total))
-        if rc == -2:
-            raise too_large
-        if rc != 0:
-            raise ValueError(f'd3h grid encoding: the library refuses this configuration (a level scale out of range?): {c}')
+        try:
+            L.call('gridenc_layout', *self._cfg_args(), scale, res, offset, size, hashed, ctypes.byref(total))
+        except L.StatusError as e:
+            if e.code == -2:
+                raise too_large from None
+            raise ValueError(f'd3h grid encoding: the library refuses this configuration (a level scale out of range?): {c}') from None
         self.scale, self.res, self.offset, self.size = [float(v) for v in scale], list(res), list(offset), list(size)
         self.hashed = [bool(v) for v in hashed]
         self.n_entries = int(total.value)
         self.n_params = self.n_entries * self.n_features
 
     def _cfg_args(self):
-        return (L.i32(self.n_dims), L.i32(self.n_levels), L.i32(self.n_features), L.i32(self.log2_hashmap_size), L.i32(self.base_resolution),
-                ctypes.c_double(self.per_level_scale), L.i32(0 if self.grid_type == 'Hash' else 1))
+        return (self.n_dims, self.n_levels, self.n_features, self.log2_hashmap_size, self.base_resolution, self.per_level_scale,
+                0 if self.grid_type == 'Hash' else 1)
 
     def _kernel_args(self):
-        return self._cfg_args() + (L.i32(0 if self.interpolation == 'Linear' else 1),)
+        return self._cfg_args() + (0 if self.interpolation == 'Linear' else 1,)
 
     def __repr__(self):
         return (f'GridConfig(D={self.n_dims}, L={self.n_levels}, F={self.n_features}, T={self.log2_hashmap_size}, base={self.base_resolution}, '
@@ -122,8 +123,7 @@ class _GridEncFn(torch.autograd.Function):
         n = xs.shape[0]
         out = torch.empty(n, cfg.n_output_dims, dtype=torch.float32, device=x.device)
         if n > 0:
-            L.check(L.lib().d3h_gridenc_fwd(L.ptr(xs), L.ptr(tab), L.i64(tab.numel()), L.i64(n), *cfg._kernel_args(), L.ptr(out), L.stream()),
-                    'gridenc_fwd')
+            L.call('gridenc_fwd', xs, tab, tab.numel(), n, *cfg._kernel_args(), out)
         ctx.save_for_backward(xs, tab)
         ctx.cfg, ctx.xshape, ctx.tshape = cfg, x.shape, table.shape
         return out
@@ -138,8 +138,7 @@ class _GridEncFn(torch.autograd.Function):
         d_tab = L.zeros_like(tab) if ctx.needs_input_grad[1] else None
         if n > 0 and (d_x is not None or d_tab is not None):
             gc = _aligned(g.reshape(n, cfg.n_output_dims).contiguous().float(), cfg.n_features)
-            L.check(L.lib().d3h_gridenc_bwd(L.ptr(xs), L.ptr(tab), L.i64(tab.numel()), L.ptr(gc), L.i64(n), *cfg._kernel_args(), L.ptr(d_tab),
-                                            L.ptr(d_x), L.stream()), 'gridenc_bwd')
+            L.call('gridenc_bwd', xs, tab, tab.numel(), gc, n, *cfg._kernel_args(), d_tab, d_x)
         return (d_x.reshape(ctx.xshape) if d_x is not None else None, d_tab.reshape(ctx.tshape) if d_tab is not None else None, None)
 
 

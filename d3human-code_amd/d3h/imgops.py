@@ -19,8 +19,7 @@ class _AutoNormalsFn(torch.autograd.Function):
         nv, nf = v.shape[-2], f32.shape[0]
         raw = torch.empty_like(v)
         vn = torch.empty_like(v)
-        L.check(L.lib().d3h_auto_normals_fwd(L.ptr(v), L.i32(nb), L.i32(nv), L.ptr(f32), L.i32(nf), L.ptr(raw), L.ptr(vn), L.stream()),
-                'auto_normals_fwd')
+        L.call('auto_normals_fwd', v, nb, nv, f32, nf, raw, vn)
         ctx.save_for_backward(v, f32, raw)
         return vn
 
@@ -30,8 +29,7 @@ class _AutoNormalsFn(torch.autograd.Function):
         nb = 1 if v.dim() == 2 else v.shape[0]
         d_v = L.zeros_like(v)
         g_raw = torch.empty_like(v)
-        L.check(L.lib().d3h_auto_normals_bwd(L.ptr(v), L.i32(nb), L.i32(v.shape[-2]), L.ptr(f32), L.i32(f32.shape[0]), L.ptr(raw),
-                                             L.ptr(g.contiguous()), L.ptr(g_raw), L.ptr(d_v), L.stream()), 'auto_normals_bwd')
+        L.call('auto_normals_bwd', v, nb, v.shape[-2], f32, f32.shape[0], raw, g.contiguous(), g_raw, d_v)
         return d_v, None
 
 
@@ -47,8 +45,7 @@ class _FaceNormalsFn(torch.autograd.Function):
         nb = 1 if v.dim() == 2 else v.shape[0]
         nf = f32.shape[0]
         fn = torch.empty(*v.shape[:-2], nf, 3, dtype=torch.float32, device=v.device)
-        L.check(L.lib().d3h_face_normals_fwd(L.ptr(v), L.i32(nb), L.i32(v.shape[-2]), L.ptr(f32), L.i32(nf), L.ptr(fn), L.stream()),
-                'face_normals_fwd')
+        L.call('face_normals_fwd', v, nb, v.shape[-2], f32, nf, fn)
         ctx.save_for_backward(v, f32)
         ctx.zeros = L.zeros_like(v) if ctx.needs_input_grad[0] else None      # d_v, filled ahead of the backward (d3h/mtets.py)
         return fn
@@ -60,8 +57,7 @@ class _FaceNormalsFn(torch.autograd.Function):
         d_v, ctx.zeros = getattr(ctx, 'zeros', None), None
         if d_v is None:
             d_v = L.zeros_like(v)
-        L.check(L.lib().d3h_face_normals_bwd(L.ptr(v), L.i32(nb), L.i32(v.shape[-2]), L.ptr(f32), L.i32(f32.shape[0]), L.ptr(g.contiguous()),
-                                             L.ptr(d_v), L.stream()), 'face_normals_bwd')
+        L.call('face_normals_bwd', v, nb, v.shape[-2], f32, f32.shape[0], g.contiguous(), d_v)
         return d_v, None
 
 
@@ -100,8 +96,7 @@ class _ShadingNormalFn(torch.autograd.Function):
         keep, strides = _bc_strides(ins, shp)
         B, H, W = shp
         out = torch.empty(B, H, W, 3, dtype=torch.float32, device=pos.device)
-        L.check(L.lib().d3h_shading_normal_fwd(*[L.ptr(t) for t in keep], strides, L.i32(B), L.i32(H), L.i32(W), L.i32(int(two_sided)),
-                                               L.i32(int(opengl)), L.ptr(out), L.stream()), 'shading_normal_fwd')
+        L.call('shading_normal_fwd', *keep, strides, B, H, W, int(two_sided), int(opengl), out)
         ctx.save_for_backward(*keep)
         ctx.meta = (shp, bool(two_sided), bool(opengl), [tuple(t.shape) for t in ins])
         return out
@@ -113,9 +108,7 @@ class _ShadingNormalFn(torch.autograd.Function):
         B, H, W = shp
         _, strides = _bc_strides(keep, shp)
         grads = [torch.empty(B, H, W, 3, dtype=torch.float32, device=g.device) for _ in range(6)]
-        L.check(L.lib().d3h_shading_normal_bwd(*[L.ptr(t) for t in keep], strides, L.i32(B), L.i32(H), L.i32(W), L.i32(int(two_sided)),
-                                               L.i32(int(opengl)), L.ptr(g.contiguous()), *[L.ptr(t) for t in grads], L.stream()),
-                'shading_normal_bwd')
+        L.call('shading_normal_bwd', *keep, strides, B, H, W, int(two_sided), int(opengl), g.contiguous(), *grads)
         outs = []
         for gr, shape in zip(grads, in_shapes):
             full = (1,) * (4 - len(shape)) + tuple(shape)
@@ -144,8 +137,7 @@ class _ImageLossFn(torch.autograd.Function):
         tgt_c = target.float().expand(img_c.shape).contiguous()
         npix = img_c.numel() // 3
         out = torch.empty(1, dtype=torch.float32, device=img.device)
-        L.check(L.lib().d3h_image_loss_fwd(L.ptr(img_c), L.ptr(tgt_c), L.i64(npix), L.i32(_LOSS[loss]), L.i32(_TONE[tonemapper]), L.ptr(out),
-                                           L.stream()), 'image_loss_fwd')
+        L.call('image_loss_fwd', img_c, tgt_c, npix, _LOSS[loss], _TONE[tonemapper], out)
         ctx.save_for_backward(img_c, tgt_c)
         ctx.meta = (loss, tonemapper, npix, img.shape, target.shape)
         return out[0] / npix
@@ -157,8 +149,7 @@ class _ImageLossFn(torch.autograd.Function):
         d_img = torch.empty_like(img_c) if ctx.needs_input_grad[0] else None
         d_tgt = torch.empty_like(tgt_c) if ctx.needs_input_grad[1] else None
         gs = g.reshape(1).contiguous().float()
-        L.check(L.lib().d3h_image_loss_bwd(L.ptr(img_c), L.ptr(tgt_c), L.i64(npix), L.i32(_LOSS[loss]), L.i32(_TONE[tonemapper]), L.ptr(gs),
-                                           L.f32(1.0 / npix), L.ptr(d_img), L.ptr(d_tgt), L.stream()), 'image_loss_bwd')
+        L.call('image_loss_bwd', img_c, tgt_c, npix, _LOSS[loss], _TONE[tonemapper], gs, 1.0 / npix, d_img, d_tgt)
         red = lambda t, s: None if t is None else t.sum_to_size(s)
         return red(d_img, ishape), red(d_tgt, tshape), None, None
 
@@ -180,8 +171,7 @@ class _SSIMFn(torch.autograd.Function):
         gmom = torch.empty(5 * N * H * W, dtype=torch.float32, device=a.device) if need else None
         out = torch.empty(1, dtype=torch.float32, device=a.device)
         need_b = bool(b.requires_grad)          # a constant second image (the target of a loss): three moment-gradient planes instead of five
-        L.check(L.lib().d3h_ssim_fwd(L.ptr(a_c), L.ptr(b_c), L.i32(N), L.i32(H), L.i32(W), L.ptr(tmp), L.ptr(gmom), L.i32(need_b), L.ptr(out), None, L.i32(1),
-                                     L.stream()), 'ssim_fwd')
+        L.call('ssim_fwd', a_c, b_c, N, H, W, tmp, gmom, need_b, out, None, 1)
         if need:
             ctx.save_for_backward(a_c, b_c, gmom)
         ctx.dims = (N, H, W)
@@ -196,8 +186,7 @@ class _SSIMFn(torch.autograd.Function):
         d_a = torch.empty_like(a_c) if ctx.needs_input_grad[0] else None
         d_b = torch.empty_like(b_c) if (ctx.needs_input_grad[1] and ctx.need_b) else None
         gs = g.reshape(1).contiguous().float()
-        L.check(L.lib().d3h_ssim_bwd(L.ptr(a_c), L.ptr(b_c), L.i32(N), L.i32(H), L.i32(W), L.ptr(gmom), L.i32(ctx.need_b), L.ptr(tmp), L.ptr(gs),
-                                     L.f32(1.0 / (N * H * W)), L.ptr(d_a), L.ptr(d_b), None, L.i32(1), L.stream()), 'ssim_bwd')
+        L.call('ssim_bwd', a_c, b_c, N, H, W, gmom, ctx.need_b, tmp, gs, 1.0 / (N * H * W), d_a, d_b, None, 1)
         return d_a, d_b
 
 
@@ -223,7 +212,7 @@ class _FirstChannelsFn(torch.autograd.Function):
         g = g.contiguous().float()
         cin, cout = int(g.shape[-1]), ctx.cout
         out = torch.empty(*g.shape[:-1], cout, dtype=torch.float32, device=g.device)
-        L.check(L.lib().d3h_channels_pad(L.ptr(g), L.i64(g.numel() // cin), L.i32(cin), L.i32(cout), L.ptr(out), L.stream()), 'channels_pad')
+        L.call('channels_pad', g, g.numel() // cin, cin, cout, out)
         return out, None
 
 
@@ -267,15 +256,10 @@ class _CompositeFn(torch.autograd.Function):
         C = sum(1 if k == COMP_ALPHA else c + 1 for k, c in zip(kinds, nch))
         out = torch.empty(B, H, W, C, dtype=torch.float32, device=dev)
         bg_t = [None if b is None else b.float().contiguous() for b in bgs]
-        P = ctypes.c_void_p * n
         I = ctypes.c_int * n
-        addr = lambda t: None if t is None else t.data_ptr()
         rc = rast.contiguous()
-        keep = [v[0] for v in views] + bg_t + [rc, out]
-        L.check(L.lib().d3h_composite_fwd(L.i32(n), P(*[addr(v[0]) for v in views]), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
-                                          P(*[addr(b) for b in bg_t]), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]),
-                                          L.ptr(rc), L.i32(B), L.i32(H), L.i32(W), L.ptr(out), L.stream()), 'composite_fwd')
-        del keep
+        L.call('composite_fwd', n, L.ptr_array([v[0] for v in views], strided=True), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds), L.ptr_array(bg_t),
+               I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]), rc, B, H, W, out)
         ctx.save_for_backward(rc)
         ctx.meta = (kinds, nch, [s.shape for s in srcs])
         return out
@@ -289,10 +273,8 @@ class _CompositeFn(torch.autograd.Function):
         n = len(nch)
         g = g.contiguous().float()
         ds = [torch.empty(B, H, W, c, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[3 + k] else None for k, c in enumerate(nch)]
-        P = ctypes.c_void_p * n
         I = ctypes.c_int * n
-        L.check(L.lib().d3h_composite_bwd(L.i32(n), P(*[None if d is None else d.data_ptr() for d in ds]), I(*nch), I(*kinds), L.ptr(rc),
-                                          L.i32(B), L.i32(H), L.i32(W), L.ptr(g), L.stream()), 'composite_bwd')
+        L.call('composite_bwd', n, L.ptr_array(ds), I(*nch), I(*kinds), rc, B, H, W, g)
         red = lambda d, shp: None if d is None else d.sum_to_size(shp)
         return (None, None, None) + tuple(red(d, shp) for d, shp in zip(ds, shapes))
 
@@ -325,15 +307,10 @@ def composite_antialias(rast, sources, pos, tri):
     bg_t = [None if b is None else b.float().contiguous() for _, _, b in sources]
     rc, pos_c, tri_c = rast.contiguous(), pos.contiguous().float(), tri.contiguous()
     flags = _R._edge_flags(pos_c, tri_c, B, H, W)
-    P = ctypes.c_void_p * n
     I = ctypes.c_int * n
-    addr = lambda t: None if t is None else t.data_ptr()
-    keep = [v[0] for v in views] + bg_t
-    L.check(L.lib().d3h_composite_antialias_fwd(L.i32(n), P(*[addr(v[0]) for v in views]), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
-                                                P(*[addr(b) for b in bg_t]), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]),
-                                                L.ptr(rc), L.ptr(pos_c), L.i32(_R._bstride(pos_c)), L.ptr(tri_c), L.i32(tri_c.shape[0]), L.ptr(flags),
-                                                L.i32(B), L.i32(H), L.i32(W), L.ptr(out), L.stream()), 'composite_antialias_fwd')
-    del keep
+    L.call('composite_antialias_fwd', n, L.ptr_array([v[0] for v in views], strided=True), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
+           L.ptr_array(bg_t), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]), rc, pos_c, _R._bstride(pos_c), tri_c,
+           tri_c.shape[0], flags, B, H, W, out)
     return out
 
 
@@ -356,15 +333,10 @@ class _CompositeAntialiasFn(torch.autograd.Function):
         bg_t = [None if b is None else b.float().contiguous() for b in bgs]
         rc, pos_c, tri_c = rast.contiguous(), pos.contiguous().float(), tri.contiguous()
         flags = _R._edge_flags(pos_c, tri_c, B, H, W)
-        P = ctypes.c_void_p * n
         I = ctypes.c_int * n
-        addr = lambda t: None if t is None else t.data_ptr()
-        keep = [v[0] for v in views] + bg_t
-        L.check(L.lib().d3h_composite_antialias_fwd(L.i32(n), P(*[addr(v[0]) for v in views]), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
-                                                    P(*[addr(b) for b in bg_t]), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]),
-                                                    L.ptr(rc), L.ptr(pos_c), L.i32(_R._bstride(pos_c)), L.ptr(tri_c), L.i32(tri_c.shape[0]), L.ptr(flags),
-                                                    L.i32(B), L.i32(H), L.i32(W), L.ptr(out), L.stream()), 'composite_antialias_fwd')
-        del keep
+        L.call('composite_antialias_fwd', n, L.ptr_array([v[0] for v in views], strided=True), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
+               L.ptr_array(bg_t), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]), rc, pos_c, _R._bstride(pos_c), tri_c,
+               tri_c.shape[0], flags, B, H, W, out)
         ctx.save_for_backward(rc, pos_c, tri_c, flags, *[v[0] for v in views], *[b for b in bg_t if b is not None])
         ctx.meta = (kinds, nch, [s.shape for s in srcs], [int(v[1]) for v in views], [b is not None for b in bg_t])
         return out
@@ -385,13 +357,10 @@ class _CompositeAntialiasFn(torch.autograd.Function):
         dch = [int(shp[-1]) for shp in shapes]                      # the gradient comes back at the width of the tensor passed in
         ds = [torch.empty(B, H, W, c, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[6 + k] else None for k, c in enumerate(dch)]
         d_pos = L.zeros_like(pos_c) if ctx.needs_input_grad[1] else None
-        P = ctypes.c_void_p * n
         I = ctypes.c_int * n
-        addr = lambda t: None if t is None else t.data_ptr()
-        L.check(L.lib().d3h_composite_antialias_bwd(L.i32(n), P(*[addr(v) for v in views]), P(*[addr(d) for d in ds]), I(*dch), I(*strides), I(*nch),
-                                                    I(*kinds), P(*[addr(b) for b in bg_t]), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]),
-                                                    L.ptr(rc), L.ptr(pos_c), L.i32(_R._bstride(pos_c)), L.ptr(tri_c), L.i32(tri_c.shape[0]), L.ptr(flags),
-                                                    L.i32(B), L.i32(H), L.i32(W), L.ptr(g), L.ptr(d_pos), L.stream()), 'composite_antialias_bwd')
+        L.call('composite_antialias_bwd', n, L.ptr_array(views, strided=True), L.ptr_array(ds), I(*dch), I(*strides), I(*nch), I(*kinds),
+               L.ptr_array(bg_t), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]), rc, pos_c, _R._bstride(pos_c), tri_c,
+               tri_c.shape[0], flags, B, H, W, g, d_pos)
         red = lambda d, shp: None if d is None else d.sum_to_size(shp)
         return (None, d_pos, None, None, None, None) + tuple(red(d, shp) for d, shp in zip(ds, shapes))
 
@@ -428,7 +397,6 @@ class _PixelLossesFn(torch.autograd.Function):
         if want_ssim:
             sa = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
             sb = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
-        lib = L.lib()
         # masked_prep: None = no extra output; () = the masked colour image shaded.rgb * ref.a; (shift[3], scale[3]) = that image mapped
         # to the LPIPS trunk input ((2 x - 1) - shift) / scale -- a second, differentiable output [B,H,W,3]
         masked = torch.empty(B, H, W, 3, dtype=torch.float32, device=dev) if masked_prep is not None else None
@@ -436,17 +404,15 @@ class _PixelLossesFn(torch.autograd.Function):
         # SSIM passes skip the bands that see nothing else -- same results; D3H_SSIM_OCC=0: every band is computed
         occ = L.zeros((B, -(-H // 32), -(-W // 64)), torch.int32, dev) if (want_ssim and SSIM_OCC) else None
         prep = (ctypes.c_float * 6)(*[float(v) for v in (list(masked_prep[0]) + list(masked_prep[1]))]) if masked_prep else None
-        L.check(lib.d3h_pixel_losses_fwd(L.ptr(st), L.i32(C), L.i32(cs), L.i32(cg), L.i32(cm), L.i32(ckg), L.i32(csg), L.i32(cng), L.ptr(cr), L.ptr(nr),
-                                         L.i32(0 if nr is None else nr.shape[-1]), L.i32(B), L.i32(H), L.i32(W), L.i32(loss), L.i32(tonemap),
-                                         L.ptr(sums), L.ptr(sa), L.ptr(sb), L.ptr(masked), prep, L.ptr(occ), L.stream()), 'pixel_losses_fwd')
+        L.call('pixel_losses_fwd', st, C, cs, cg, cm, ckg, csg, cng, cr, nr, 0 if nr is None else nr.shape[-1], B, H, W, loss, tonemap, sums, sa, sb,
+               masked, prep, occ)
         gmom = None
         need = stacked.requires_grad
         if want_ssim:
             N = 3 * B
             tmp = None
             gmom = torch.empty(5 * N * H * W, dtype=torch.float32, device=dev) if need else None
-            L.check(lib.d3h_ssim_fwd(L.ptr(sa), L.ptr(sb), L.i32(N), L.i32(H), L.i32(W), L.ptr(tmp), L.ptr(gmom), L.i32(0), L.ptr(sums[9:]), L.ptr(occ),
-                                     L.i32(3), L.stream()), 'ssim_fwd')          # (0: the masked target is a constant)
+            L.call('ssim_fwd', sa, sb, N, H, W, tmp, gmom, 0, sums[9:], occ, 3)          # (0: the masked target is a constant)
         else:
             sums[9:].zero_()
         scale = _const([1.0 / npix] * 4 + [1.0 / (3 * npix), 1.0 / npix, 1.0 / npix, 1.0 / (3 * npix), 1.0 / (3 * npix), 1.0 / (3 * npix)], dev) \
@@ -461,7 +427,6 @@ class _PixelLossesFn(torch.autograd.Function):
     def backward(ctx, g, g_masked=None):
         st, cr, nr, sa, sb, gmom, scale, occ = ctx.saved_tensors
         B, H, W, C, cs, cg, cm, ckg, csg, cng, loss, tonemap, want_ssim, prep = ctx.cfg
-        lib = L.lib()
         gs = (g.float() * scale).contiguous() if g is not None else torch.zeros(10, dtype=torch.float32, device=st.device)
         gm = g_masked.contiguous().float() if g_masked is not None else None
         d_a = None
@@ -469,12 +434,10 @@ class _PixelLossesFn(torch.autograd.Function):
             N = 3 * B
             tmp = None
             d_a = torch.empty_like(sa)
-            L.check(lib.d3h_ssim_bwd(L.ptr(sa), L.ptr(sb), L.i32(N), L.i32(H), L.i32(W), L.ptr(gmom), L.i32(0), L.ptr(tmp), L.ptr(gs[9:]), L.f32(1.0),
-                                     L.ptr(d_a), L.ptr(None), L.ptr(occ), L.i32(3), L.stream()), 'ssim_bwd')
+            L.call('ssim_bwd', sa, sb, N, H, W, gmom, 0, tmp, gs[9:], 1.0, d_a, None, occ, 3)
         d_st = torch.empty_like(st)
-        L.check(lib.d3h_pixel_losses_bwd(L.ptr(st), L.i32(C), L.i32(cs), L.i32(cg), L.i32(cm), L.i32(ckg), L.i32(csg), L.i32(cng), L.ptr(cr), L.ptr(nr),
-                                         L.i32(0 if nr is None else nr.shape[-1]), L.i32(B), L.i32(H), L.i32(W), L.i32(loss), L.i32(tonemap),
-                                         L.ptr(gs), L.ptr(d_a), L.ptr(gm), prep if gm is not None else None, L.ptr(d_st), L.stream()), 'pixel_losses_bwd')
+        L.call('pixel_losses_bwd', st, C, cs, cg, cm, ckg, csg, cng, cr, nr, 0 if nr is None else nr.shape[-1], B, H, W, loss, tonemap, gs, d_a, gm,
+               prep if gm is not None else None, d_st)
         return (d_st,) + (None,) * 12
 
 
@@ -512,8 +475,7 @@ class _SeqLossesFn(torch.autograd.Function):
         lab = label.float().expand(B, H, W).contiguous()
         ga, gc, gb = c4(gt_all), c4(gt_cloth), c4(gt_body)
         sums = torch.empty(6, dtype=torch.float32, device=st.device)
-        L.check(L.lib().d3h_seq_losses_fwd(L.ptr(st), L.i32(C), L.i32(cs), L.i32(ca), L.ptr(lab), L.ptr(ga), L.ptr(gc), L.ptr(gb), L.i64(npix), L.i32(loss),
-                                           L.i32(tonemap), L.ptr(sums), L.stream()), 'seq_losses_fwd')
+        L.call('seq_losses_fwd', st, C, cs, ca, lab, ga, gc, gb, npix, loss, tonemap, sums)
         ctx.save_for_backward(st, lab, ga, gc, gb)
         ctx.cfg = (C, cs, ca, loss, tonemap, npix)
         return sums * (1.0 / max(npix, 1))
@@ -524,8 +486,7 @@ class _SeqLossesFn(torch.autograd.Function):
         C, cs, ca, loss, tonemap, npix = ctx.cfg
         gs = (g.float() * (1.0 / max(npix, 1))).contiguous()
         d_st = torch.empty_like(st)
-        L.check(L.lib().d3h_seq_losses_bwd(L.ptr(st), L.i32(C), L.i32(cs), L.i32(ca), L.ptr(lab), L.ptr(ga), L.ptr(gc), L.ptr(gb), L.i64(npix), L.i32(loss),
-                                           L.i32(tonemap), L.ptr(gs), L.ptr(d_st), L.stream()), 'seq_losses_bwd')
+        L.call('seq_losses_bwd', st, C, cs, ca, lab, ga, gc, gb, npix, loss, tonemap, gs, d_st)
         return (d_st,) + (None,) * 8
 
 
@@ -544,7 +505,7 @@ class _SdfRegFn(torch.autograd.Function):
     def forward(ctx, sdf, edges32, marks):
         s = sdf.reshape(-1).contiguous().float()
         sums = torch.empty(2, dtype=torch.float32, device=s.device)
-        L.check(L.lib().d3h_sdf_reg_fwd(L.ptr(s), L.ptr(edges32), L.i32(edges32.shape[0]), L.ptr(sums), L.ptr(marks), L.stream()), 'sdf_reg_fwd')
+        L.call('sdf_reg_fwd', s, edges32, edges32.shape[0], sums, marks)
         ctx.save_for_backward(s, edges32, sums)
         ctx.shape = sdf.shape
         return sums[0] / sums[1]
@@ -554,8 +515,7 @@ class _SdfRegFn(torch.autograd.Function):
         s, edges32, sums = ctx.saved_tensors
         d = L.zeros_like(s)
         gs = g.reshape(1).contiguous().float()
-        L.check(L.lib().d3h_sdf_reg_bwd(L.ptr(s), L.ptr(edges32), L.i32(edges32.shape[0]), L.ptr(sums), L.ptr(gs), L.ptr(d), L.stream()),
-                'sdf_reg_bwd')
+        L.call('sdf_reg_bwd', s, edges32, edges32.shape[0], sums, gs, d)
         return d.reshape(ctx.shape), None, None
 
 
@@ -573,7 +533,7 @@ class _XfmPointsFn(torch.autograd.Function):
         M = mtx.detach().contiguous().float()
         nb, n = M.shape[0], p.shape[1]
         out = torch.empty(nb, n, 4, dtype=torch.float32, device=p.device)
-        L.check(L.lib().d3h_xfm_points_fwd(L.ptr(p), L.i32(p.shape[0]), L.ptr(M), L.i32(nb), L.i32(n), L.f32(w), L.ptr(out), L.stream()), 'xfm_points_fwd')
+        L.call('xfm_points_fwd', p, p.shape[0], M, nb, n, w, out)
         ctx.save_for_backward(M)
         ctx.pshape = p.shape
         return out
@@ -583,8 +543,7 @@ class _XfmPointsFn(torch.autograd.Function):
         M, = ctx.saved_tensors
         nbp, n, _ = ctx.pshape
         d = torch.empty(ctx.pshape, dtype=torch.float32, device=g.device)
-        L.check(L.lib().d3h_xfm_points_bwd(L.ptr(g.contiguous().float()), L.i32(nbp), L.ptr(M), L.i32(M.shape[0]), L.i32(n), L.ptr(d), L.stream()),
-                'xfm_points_bwd')
+        L.call('xfm_points_bwd', g.contiguous().float(), nbp, M, M.shape[0], n, d)
         return d, None, None
 
 
@@ -604,8 +563,7 @@ class _LpipsHeadFn(torch.autograd.Function):
         fmt = torch.channels_last if cl else torch.contiguous_format
         f0c, n1c = f0.contiguous(memory_format=fmt).float(), n1.contiguous(memory_format=fmt).float()
         out = torch.empty(B, dtype=torch.float32, device=f0c.device)
-        L.check(L.lib().d3h_lpips_head_fwd(L.ptr_any(f0c), L.ptr_any(n1c), L.ptr(w), L.i32(B), L.i32(C), L.i32(H * W), L.i32(int(cl)), L.ptr(out),
-                                           L.stream()), 'lpips_head_fwd')
+        L.call('lpips_head_fwd', L.ptr_any(f0c), L.ptr_any(n1c), w, B, C, H * W, int(cl), out)
         ctx.save_for_backward(f0c, n1c, w)
         ctx.cl = cl
         return out
@@ -615,8 +573,7 @@ class _LpipsHeadFn(torch.autograd.Function):
         f0c, n1c, w = ctx.saved_tensors
         B, C, H, W = f0c.shape
         d = torch.empty_like(f0c)                       # preserves the memory format
-        L.check(L.lib().d3h_lpips_head_bwd(L.ptr_any(f0c), L.ptr_any(n1c), L.ptr(w), L.i32(B), L.i32(C), L.i32(H * W), L.i32(int(ctx.cl)),
-                                           L.ptr(g.contiguous().float()), L.ptr_any(d), L.stream()), 'lpips_head_bwd')
+        L.call('lpips_head_bwd', L.ptr_any(f0c), L.ptr_any(n1c), w, B, C, H * W, int(ctx.cl), g.contiguous().float(), L.ptr_any(d))
         return d, None, None
 
 
@@ -633,7 +590,6 @@ class _MaterialGradsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tex, texj, nrm, nrmj, mask, mask_tap, want_kd=True):
-        lib = L.lib()
         shp = tex.shape[:-1]
         c = lambda t: None if t is None else t.contiguous().float()
         tex, texj, nrm, nrmj, mask, mask_tap = c(tex), c(texj), c(nrm), c(nrmj), c(mask), c(mask_tap)
@@ -642,8 +598,7 @@ class _MaterialGradsFn(torch.autograd.Function):
         kd = new() if want_kd else None
         kdg, ksg = (new(), new()) if texj is not None else (None, None)
         ng = new() if nrm is not None else None
-        L.check(lib.d3h_material_grads_fwd(L.ptr(tex), L.ptr(texj), L.ptr(nrm), L.ptr(nrmj), L.ptr(mask), L.ptr(mask_tap), L.i64(n), L.ptr(kd),
-                                           L.ptr(kdg), L.ptr(ksg), L.ptr(ng), L.stream()), 'material_grads_fwd')
+        L.call('material_grads_fwd', tex, texj, nrm, nrmj, mask, mask_tap, n, kd, kdg, ksg, ng)
         ctx.save_for_backward(tex, texj, nrm, nrmj, mask, mask_tap)
         ctx.shp = shp
         return kd, kdg, ksg, ng
@@ -651,7 +606,6 @@ class _MaterialGradsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_kd, g_kdg, g_ksg, g_ng):
         tex, texj, nrm, nrmj, mask, mask_tap = ctx.saved_tensors
-        lib = L.lib()
         shp = ctx.shp
         n = tex.numel() // 6
         c = lambda t: None if t is None else t.contiguous().float()
@@ -663,9 +617,7 @@ class _MaterialGradsFn(torch.autograd.Function):
         d_nrm = torch.empty(*shp, 3, dtype=torch.float32, device=tex.device) if need_nrm else None
         d_nrmj = torch.empty_like(d_nrm) if need_nrm else None
         if need_tex or need_nrm:
-            L.check(lib.d3h_material_grads_bwd(L.ptr(tex), L.ptr(texj), L.ptr(nrm), L.ptr(nrmj), L.ptr(mask), L.ptr(mask_tap), L.i64(n), L.ptr(g_kd),
-                                               L.ptr(g_kdg), L.ptr(g_ksg), L.ptr(g_ng), L.ptr(d_tex), L.ptr(d_texj), L.ptr(d_nrm), L.ptr(d_nrmj),
-                                               L.stream()), 'material_grads_bwd')
+            L.call('material_grads_bwd', tex, texj, nrm, nrmj, mask, mask_tap, n, g_kd, g_kdg, g_ksg, g_ng, d_tex, d_texj, d_nrm, d_nrmj)
         return d_tex, d_texj, d_nrm, d_nrmj, None, None, None
 
 

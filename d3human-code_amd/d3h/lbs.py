@@ -60,23 +60,19 @@ class KnnGrid:
         """nearest template vertex of the first counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` (a buffer at its capacity), the row
         count read on the DEVICE (d3h/mtets.py: work queued before the host knows the sizes of the extraction) -> idx [capacity] int32.
         `counts`: the extraction's counter block of at least 11 int32 (entry 10 is its overflow flag: when set, nothing is written)"""
-        lib = L.lib()
         pts = _capacity_points(pts_cap, 'query_counted')
         _check_counts(counts, pts, 'query_counted')
         idx = torch.empty(pts.shape[0], dtype=torch.int32, device=pts.device)
-        L.check(lib.d3h_knn1_grid_counted(L.ptr(pts), L.i32(pts.shape[0]), L.ptr(counts), L.ptr(self.cell_pts), L.ptr(self.cell_start),
-                                          L.ptr(self.cell_seed), L.i32(self.nv), self.lo, L.f32(self.h), L.i32(self.g[0]), L.i32(self.g[1]),
-                                          L.i32(self.g[2]), L.ptr(idx), L.stream()), 'knn1_grid_counted')
+        L.call('knn1_grid_counted', pts, pts.shape[0], counts, self.cell_pts, self.cell_start, self.cell_seed, self.nv, self.lo, self.h, self.g[0],
+               self.g[1], self.g[2], idx)
         return idx
 
     def query(self, pts, want_dist=False):
-        lib = L.lib()
         pts = pts.detach().contiguous().float()
         idx = torch.empty(pts.shape[0], dtype=torch.int32, device=pts.device)
         dist = torch.empty(pts.shape[0], dtype=torch.float32, device=pts.device) if want_dist else None
-        L.check(lib.d3h_knn1_grid(L.ptr(pts), L.i32(pts.shape[0]), L.ptr(self.cell_pts), L.ptr(self.cell_start), L.ptr(self.cell_seed), L.i32(self.nv),
-                                  self.lo, L.f32(self.h), L.i32(self.g[0]), L.i32(self.g[1]), L.i32(self.g[2]), L.ptr(idx),
-                                  L.ptr(dist), L.stream()), 'knn1_grid')
+        L.call('knn1_grid', pts, pts.shape[0], self.cell_pts, self.cell_start, self.cell_seed, self.nv, self.lo, self.h, self.g[0], self.g[1],
+               self.g[2], idx, dist)
         return (idx, dist) if want_dist else idx
 
     def query_k(self, pts, K):
@@ -85,8 +81,7 @@ class KnnGrid:
         P = pts.shape[0]
         idx = torch.empty(P, K, dtype=torch.int32, device=pts.device)
         d2 = torch.empty(P, K, dtype=torch.float32, device=pts.device)
-        L.check(L.lib().d3h_knnk_grid(L.ptr(pts), L.i32(P), L.ptr(self.cell_pts), L.ptr(self.cell_start), L.i32(self.nv), self.lo, L.f32(self.h),
-                                      L.i32(self.g[0]), L.i32(self.g[1]), L.i32(self.g[2]), L.i32(K), L.ptr(idx), L.ptr(d2), L.stream()), 'knnk_grid')
+        L.call('knnk_grid', pts, P, self.cell_pts, self.cell_start, self.nv, self.lo, self.h, self.g[0], self.g[1], self.g[2], K, idx, d2)
         return KnnResult(idx, d2)
 
     def query_k_counted(self, pts_cap, counts, K, out=None):
@@ -98,9 +93,8 @@ class KnnGrid:
         if out is None:
             out = KnnResult(torch.empty(cap, K, dtype=torch.int32, device=pts.device), torch.empty(cap, K, dtype=torch.float32, device=pts.device))
         _check_knn_result(out, cap, K, 'query_k_counted')
-        L.check(L.lib().d3h_knnk_grid_counted(L.ptr(pts), L.i32(cap), L.ptr(counts), L.ptr(self.cell_pts), L.ptr(self.cell_start), L.i32(self.nv),
-                                              self.lo, L.f32(self.h), L.i32(self.g[0]), L.i32(self.g[1]), L.i32(self.g[2]), L.i32(K), L.ptr(out.idx),
-                                              L.ptr(out.d2), L.stream()), 'knnk_grid_counted')
+        L.call('knnk_grid_counted', pts, cap, counts, self.cell_pts, self.cell_start, self.nv, self.lo, self.h, self.g[0], self.g[1], self.g[2], K,
+               out.idx, out.d2)
         return out
 
 
@@ -202,7 +196,7 @@ def knnk(pts, tmpl, K, grid=None):
     P = pts.shape[0]
     idx = torch.empty(P, K, dtype=torch.int32, device=pts.device)
     d2 = torch.empty(P, K, dtype=torch.float32, device=pts.device)
-    L.check(L.lib().d3h_knnk(L.ptr(pts), L.i32(P), L.ptr(tmpl), L.i32(tmpl.shape[0]), L.i32(K), L.ptr(idx), L.ptr(d2), L.stream()), 'knnk')
+    L.call('knnk', pts, P, tmpl, tmpl.shape[0], K, idx, d2)
     return KnnResult(idx, d2)
 
 
@@ -211,18 +205,16 @@ def knn1(pts, tmpl, grid=None):
     `tmpl` (fixed templates: same result, ~10x faster)"""
     if grid is not None:
         return grid.query(pts)
-    lib = L.lib()
     pts = pts.detach().contiguous().float()
     tmpl = tmpl.detach().contiguous().float()
     idx = torch.empty(pts.shape[0], dtype=torch.int32, device=pts.device)
-    L.check(lib.d3h_knn1(L.ptr(pts), L.i32(pts.shape[0]), L.ptr(tmpl), L.i32(tmpl.shape[0]), L.ptr(idx), None, L.stream()), 'knn1')
+    L.call('knn1', pts, pts.shape[0], tmpl, tmpl.shape[0], idx, None)
     return idx
 
 
 class _LBSFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pts, idx, lbs_w, A0, A, trans, pre):
-        lib = L.lib()
         pts_c = pts.contiguous().float()
         A0c = A0.detach().reshape(-1, 16).contiguous().float()
         Ac = A.detach().reshape(A.shape[0], -1, 16).contiguous().float()
@@ -234,8 +226,7 @@ class _LBSFn(torch.autograd.Function):
             out = pre
         else:
             out = torch.empty(nb, P, 3, dtype=torch.float32, device=pts.device)
-            L.check(lib.d3h_lbs_fwd(L.ptr(pts_c), L.i32(P), L.ptr(idx), L.ptr(lbs_w), L.i32(nj), L.ptr(A0c), L.ptr(Ac), L.ptr(tr),
-                                    L.i32(nb), L.ptr(out), None, L.stream()), 'lbs_fwd')
+            L.call('lbs_fwd', pts_c, P, idx, lbs_w, nj, A0c, Ac, tr, nb, out, None)
         ctx.save_for_backward(pts_c, idx, lbs_w, A0c, Ac)
         ctx.shapes = (A.shape, trans.shape)
         return out
@@ -243,7 +234,6 @@ class _LBSFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         pts, idx, lbs_w, A0c, Ac = ctx.saved_tensors
-        lib = L.lib()
         nb, nj, P = Ac.shape[0], Ac.shape[1], pts.shape[0]
         g = g.contiguous().float()
         d_pts = torch.empty_like(pts)
@@ -251,8 +241,7 @@ class _LBSFn(torch.autograd.Function):
         need_A, need_t = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
         dA = L.zeros((nb, nj, 16), torch.float32, pts.device) if need_A else None
         dT = L.zeros((nb, 3), torch.float32, pts.device) if need_t else None
-        L.check(lib.d3h_lbs_bwd(L.ptr(pts), L.i32(P), L.ptr(idx), L.ptr(lbs_w), L.i32(nj), L.ptr(A0c), L.ptr(Ac), L.i32(nb), L.ptr(g),
-                                L.ptr(d_pts), L.ptr(per_frame), L.ptr(dA), L.ptr(dT), L.stream()), 'lbs_bwd')
+        L.call('lbs_bwd', pts, P, idx, lbs_w, nj, A0c, Ac, nb, g, d_pts, per_frame, dA, dT)
         a_shape, t_shape = ctx.shapes
         return (d_pts, None, None, None, dA.reshape(a_shape) if need_A else None, dT.reshape(t_shape) if need_t else None, None)
 
@@ -270,7 +259,6 @@ def lbs_points_counted(pts_cap, counts, idx_cap, lbs_w, A0, A, trans):
     is queued before the host knows r.  -> a flat float buffer whose leading B * r * 3 floats are the dense [B, r, 3] result (narrow it with
     counted_result once r is known and hand it to lbs_points(..., pre=)).  `counts`: the extraction's counter block of at least 11 int32;
     entry 10 is its overflow flag: when set, nothing is written"""
-    lib = L.lib()
     pts = _capacity_points(pts_cap, 'lbs_points_counted')
     _check_counts(counts, pts, 'lbs_points_counted')
     _lbs_args(pts, idx_cap, lbs_w, A0, A, trans, 'lbs_points_counted')
@@ -279,8 +267,7 @@ def lbs_points_counted(pts_cap, counts, idx_cap, lbs_w, A0, A, trans):
     tr = trans.detach().reshape(-1, 3).contiguous().float()
     nb, nj, cap = Ac.shape[0], Ac.shape[1], pts_cap.shape[0]
     out = torch.empty(nb * cap * 3, dtype=torch.float32, device=pts_cap.device)
-    L.check(lib.d3h_lbs_fwd_counted(L.ptr(pts), L.i32(cap), L.ptr(counts), L.ptr(idx_cap), L.ptr(lbs_w.contiguous().float()), L.i32(nj),
-                                    L.ptr(A0c), L.ptr(Ac), L.ptr(tr), L.i32(nb), L.ptr(out), L.stream()), 'lbs_fwd_counted')
+    L.call('lbs_fwd_counted', pts, cap, counts, idx_cap, lbs_w.contiguous().float(), nj, A0c, Ac, tr, nb, out)
     return out
 
 
@@ -304,7 +291,6 @@ class _LBSKFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pts, idx, d2, lbs_w, tmpl, A0, A, trans, pre):
-        lib = L.lib()
         pts_c = pts.contiguous().float()
         P = pts_c.shape[0]
         K, A0c, Ac, tr = _lbsk_args(KnnResult(idx, d2), lbs_w, tmpl, A0, A, trans, P, 'lbs_points_k')
@@ -315,8 +301,7 @@ class _LBSKFn(torch.autograd.Function):
             out = pre
         else:
             out = torch.empty(nb, P, 3, dtype=torch.float32, device=pts.device)
-            L.check(lib.d3h_lbsk_fwd(L.ptr(pts_c), L.i32(P), L.ptr(idx), L.ptr(d2), L.i32(K), L.ptr(lbs_w), L.i32(nj), L.ptr(A0c), L.ptr(Ac),
-                                     L.ptr(tr), L.i32(nb), L.ptr(out), None, L.stream()), 'lbsk_fwd')
+            L.call('lbsk_fwd', pts_c, P, idx, d2, K, lbs_w, nj, A0c, Ac, tr, nb, out, None)
         ctx.save_for_backward(pts_c, idx, d2, lbs_w, tmpl, A0c, Ac)
         ctx.shapes = (A.shape, trans.shape)
         return out
@@ -324,7 +309,6 @@ class _LBSKFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         pts, idx, d2, lbs_w, tmpl, A0c, Ac = ctx.saved_tensors
-        lib = L.lib()
         nb, nj, P, K = Ac.shape[0], Ac.shape[1], pts.shape[0], idx.shape[1]
         g = g.contiguous().float()
         need_p, need_A, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[6], ctx.needs_input_grad[7]
@@ -332,8 +316,7 @@ class _LBSKFn(torch.autograd.Function):
         per_frame = torch.empty(nb, P, 3, dtype=torch.float32, device=pts.device) if need_p and nb > 1 else None   # summed in frame order
         dA = L.zeros((nb, nj, 16), torch.float32, pts.device) if need_A else None
         dT = L.zeros((nb, 3), torch.float32, pts.device) if need_t else None
-        L.check(lib.d3h_lbsk_bwd(L.ptr(pts), L.i32(P), L.ptr(idx), L.ptr(d2), L.i32(K), L.ptr(tmpl), L.ptr(lbs_w), L.i32(nj), L.ptr(A0c),
-                                 L.ptr(Ac), L.i32(nb), L.ptr(g), L.ptr(d_pts), L.ptr(per_frame), L.ptr(dA), L.ptr(dT), L.stream()), 'lbsk_bwd')
+        L.call('lbsk_bwd', pts, P, idx, d2, K, tmpl, lbs_w, nj, A0c, Ac, nb, g, d_pts, per_frame, dA, dT)
         a_shape, t_shape = ctx.shapes
         return (d_pts, None, None, None, None, None, dA.reshape(a_shape) if need_A else None, dT.reshape(t_shape) if need_t else None, None)
 
@@ -352,16 +335,13 @@ def lbs_points_k_counted(pts_cap, counts, nn_cap, lbs_w, tmpl, A0, A, trans):
     """lbs_points_k over the first r = counts[0] + 3 counts[1] + 4 counts[2] rows of `pts_cap` [capacity, 3] (nn_cap: query_k_counted of the same
     buffer), r read on the DEVICE.  -> a flat float buffer whose leading B * r * 3 floats are the dense [B, r, 3] result (counted_result).
     `counts`: as in lbs_points_counted"""
-    lib = L.lib()
     pts = _capacity_points(pts_cap, 'lbs_points_k_counted')
     _check_counts(counts, pts, 'lbs_points_k_counted')
     cap = pts.shape[0]
     K, A0c, Ac, tr = _lbsk_args(nn_cap, lbs_w, tmpl, A0, A, trans, cap, 'lbs_points_k_counted')
     nb, nj = Ac.shape[0], Ac.shape[1]
     out = torch.empty(nb * cap * 3, dtype=torch.float32, device=pts.device)
-    L.check(lib.d3h_lbsk_fwd_counted(L.ptr(pts), L.i32(cap), L.ptr(counts), L.ptr(nn_cap.idx), L.ptr(nn_cap.d2), L.i32(K),
-                                     L.ptr(lbs_w.detach().contiguous().float()), L.i32(nj), L.ptr(A0c), L.ptr(Ac), L.ptr(tr), L.i32(nb), L.ptr(out),
-                                     L.stream()), 'lbsk_fwd_counted')
+    L.call('lbsk_fwd_counted', pts, cap, counts, nn_cap.idx, nn_cap.d2, K, lbs_w.detach().contiguous().float(), nj, A0c, Ac, tr, nb, out)
     return out
 
 

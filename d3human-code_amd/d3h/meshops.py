@@ -70,8 +70,7 @@ class _LaplacianLossFn(torch.autograd.Function):
         nv = vc.shape[0]
         lv = torch.empty_like(vc)
         s = torch.empty(1, dtype=torch.float32, device=vc.device)
-        L.check(L.lib().d3h_laplacian_loss_fwd(L.ptr(vc), L.i32(nv), L.ptr(topo.offs), L.ptr(topo.nbr), L.ptr(topo.inv_deg), L.ptr(lv), L.ptr(s),
-                                               L.stream()), 'laplacian_loss_fwd')
+        L.call('laplacian_loss_fwd', vc, nv, topo.offs, topo.nbr, topo.inv_deg, lv, s)
         ctx.save_for_backward(lv)
         ctx.topo = topo
         return s[0] / nv
@@ -83,8 +82,7 @@ class _LaplacianLossFn(torch.autograd.Function):
         nv = lv.shape[0]
         d_v = torch.empty_like(lv)
         gs = g.reshape(1).contiguous().float()
-        L.check(L.lib().d3h_laplacian_loss_bwd(L.ptr(lv), L.i32(nv), L.ptr(topo.offs), L.ptr(topo.nbr), L.ptr(topo.inv_deg), L.ptr(gs),
-                                               L.f32(2.0 / nv), L.ptr(d_v), L.stream()), 'laplacian_loss_bwd')
+        L.call('laplacian_loss_bwd', lv, nv, topo.offs, topo.nbr, topo.inv_deg, gs, 2.0 / nv, d_v)
         return d_v, None
 
 
@@ -99,7 +97,7 @@ class _NormalConsistencyFn(torch.autograd.Function):
         vc = v.contiguous().float()
         n = pairs32.shape[0]
         s = torch.empty(1, dtype=torch.float32, device=vc.device)
-        L.check(L.lib().d3h_normal_consistency_fwd(L.ptr(vc), L.ptr(faces32), L.ptr(pairs32), L.i32(n), L.ptr(s), L.stream()), 'normal_consistency_fwd')
+        L.call('normal_consistency_fwd', vc, faces32, pairs32, n, s)
         ctx.save_for_backward(vc, faces32, pairs32)
         return s[0] / n
 
@@ -109,8 +107,7 @@ class _NormalConsistencyFn(torch.autograd.Function):
         n = pairs32.shape[0]
         d_v = L.zeros_like(vc)
         gs = g.reshape(1).contiguous().float()
-        L.check(L.lib().d3h_normal_consistency_bwd(L.ptr(vc), L.ptr(faces32), L.ptr(pairs32), L.i32(n), L.ptr(gs), L.f32(1.0 / n), L.ptr(d_v),
-                                                   L.stream()), 'normal_consistency_bwd')
+        L.call('normal_consistency_bwd', vc, faces32, pairs32, n, gs, 1.0 / n, d_v)
         return d_v, None, None
 
 
@@ -125,11 +122,10 @@ class _CollisionFn(torch.autograd.Function):
         cc, bc = cloth.contiguous().float(), body.contiguous().float()
         nc, nf = cc.shape[0], faces32.shape[0]
         centers = torch.empty(nf, 3, dtype=torch.float32, device=cc.device)
-        L.check(L.lib().d3h_face_centers(L.ptr(bc), L.ptr(faces32), L.i32(nf), L.ptr(centers), L.stream()), 'face_centers')
+        L.call('face_centers', bc, faces32, nf, centers)
         nn = _lbs.knn1(cc, centers)                      # knn_points(cloth, centres, K=1): squared L2, first minimum wins
         s = torch.empty(1, dtype=torch.float32, device=cc.device)
-        L.check(L.lib().d3h_collision_fwd(L.ptr(cc), L.i32(nc), L.ptr(bc), L.ptr(faces32), L.ptr(nn), L.f32(push_eps), L.ptr(s), L.stream()),
-                'collision_fwd')
+        L.call('collision_fwd', cc, nc, bc, faces32, nn, push_eps, s)
         ctx.save_for_backward(cc, bc, faces32, nn)
         ctx.eps = float(push_eps)
         return s[0] / nc
@@ -141,8 +137,7 @@ class _CollisionFn(torch.autograd.Function):
         d_c = torch.empty_like(cc) if ctx.needs_input_grad[0] else None
         d_b = L.zeros_like(bc) if ctx.needs_input_grad[1] else None
         gs = g.reshape(1).contiguous().float()
-        L.check(L.lib().d3h_collision_bwd(L.ptr(cc), L.i32(nc), L.ptr(bc), L.ptr(faces32), L.ptr(nn), L.f32(ctx.eps), L.ptr(gs), L.f32(1.0 / nc),
-                                          L.ptr(d_c), L.ptr(d_b), L.stream()), 'collision_bwd')
+        L.call('collision_bwd', cc, nc, bc, faces32, nn, ctx.eps, gs, 1.0 / nc, d_c, d_b)
         return d_c, d_b, None, None
 
 
@@ -161,7 +156,7 @@ def mesh_sdf(points, verts, faces):
     v = verts.detach().contiguous().float()
     f = faces if faces.dtype == torch.int32 else faces.int()
     out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
-    L.check(L.lib().d3h_mesh_sdf(L.ptr(p), L.i32(p.shape[0]), L.ptr(v), L.ptr(f.contiguous()), L.i32(f.shape[0]), L.ptr(out), L.stream()), 'mesh_sdf')
+    L.call('mesh_sdf', p, p.shape[0], v, f.contiguous(), f.shape[0], out)
     return out
 
 
@@ -180,7 +175,7 @@ def mesh_wsdf(points, verts, faces, want_sdf=True, want_w=True, check=True):
         raise RuntimeError('mesh_wsdf: a face index outside [0, V)')
     sdf = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if want_sdf else None
     w = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if want_w else None
-    L.check(L.lib().d3h_mesh_wsdf(L.ptr(p), L.i32(p.shape[0]), L.ptr(v), L.ptr(f), L.i32(f.shape[0]), L.ptr(sdf), L.ptr(w), L.stream()), 'mesh_wsdf')
+    L.call('mesh_wsdf', p, p.shape[0], v, f, f.shape[0], sdf, w)
     return sdf, w
 
 
@@ -197,8 +192,7 @@ def collision_push(v, normals, field, eps=0.005, margin=0.002, rounds=100, stop_
     for _ in range(int(rounds)):
         s = field(x).contiguous().float()
         moved.zero_()
-        L.check(L.lib().d3h_collision_push(L.ptr(x), L.ptr(nrm), L.ptr(s), L.i32(n), L.f32(margin), L.f32(eps), L.ptr(moved), L.ptr(pushes), L.stream()),
-                'collision_push')
+        L.call('collision_push', x, nrm, s, n, margin, eps, moved, pushes)
         if stop_when_still and int(moved.item()) == 0:
             break
     return x, pushes

@@ -36,16 +36,15 @@ _MAXKEY = 0x7fffffffffffffff
 
 
 def _round(v, f, thr, mask):
-    lib, dev = L.lib(), v.device
+    dev = v.device
     n, nf = int(v.shape[0]), int(f.shape[0])
-    idx64 = L.i32(f.dtype == torch.int64)
+    idx64 = f.dtype == torch.int64
     lg = _mt._table_log2(3 * nf, 0, 'refine_mark')
     keys = torch.empty(1 << lg, dtype=torch.int64, device=dev)
     counts = torch.empty(1 << lg, dtype=torch.int32, device=dev)
     mark = torch.empty(1 << lg, dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    L.check(lib.d3h_refine_mark(L.ptr(v), L.ptr(f), idx64, L.i64(nf), L.i64(n), L.ptr(mask), L.f32(thr), L.ptr(keys), L.ptr(counts), L.ptr(mark), L.ptr(err),
-                                L.stream()), 'refine_mark')
+    L.call('refine_mark', v, f, idx64, nf, n, mask, thr, keys, counts, mark, err)
     marked = mark > 0
     skeys = torch.sort(torch.where(marked, keys, torch.full_like(keys, _MAXKEY))).values          # the marked keys first, ascending
     nm, extra, word = torch.stack([marked.sum(), (counts.long() * marked).sum(), err[0].long()]).tolist()      # the round's one read-back
@@ -55,7 +54,7 @@ def _round(v, f, thr, mask):
     skeys = skeys[:nm].contiguous()
     rank = torch.empty(nf, 3, dtype=torch.int32, device=dev)
     count = torch.empty(nf, dtype=torch.int32, device=dev)
-    L.check(lib.d3h_refine_count(L.ptr(f), idx64, L.i64(nf), L.i64(n), L.ptr(skeys), L.i64(nm), L.ptr(rank), L.ptr(count), L.stream()), 'refine_count')
+    L.call('refine_count', f, idx64, nf, n, skeys, nm, rank, count)
     incl = torch.cumsum(count, 0, dtype=torch.int64)
     offs = (incl - count).contiguous()
     nout = nf + extra
@@ -63,8 +62,7 @@ def _round(v, f, thr, mask):
     vout[:n] = v
     fout = torch.empty(nout, 3, dtype=f.dtype, device=dev)
     parent = torch.empty(nout, dtype=torch.int32, device=dev)
-    L.check(lib.d3h_refine_split(L.ptr(v), L.ptr(f), idx64, L.i64(nf), L.i64(n), L.ptr(skeys), L.i64(nm), L.ptr(rank), L.ptr(offs), L.i64(nout), L.ptr(vout),
-                                 L.ptr(fout), L.ptr(parent), L.stream()), 'refine_split')
+    L.call('refine_split', v, f, idx64, nf, n, skeys, nm, rank, offs, nout, vout, fout, parent)
     return vout, fout, parent.long()
 
 
@@ -111,6 +109,5 @@ def relax(v, faces, free_mask, iterations):
         raise RuntimeError('relax: a face index outside [0, nv)')
     topo = _mo.EdgeTopology(_mo.find_edges(f.long()), n)
     b = torch.empty_like(a)
-    L.check(L.lib().d3h_relax(L.ptr(a), L.ptr(b), L.i32(n), L.ptr(topo.offs), L.ptr(topo.nbr), L.ptr(free_mask.to(torch.uint8).contiguous()), L.i32(it),
-                              L.stream()), 'relax')
+    L.call('relax', a, b, n, topo.offs, topo.nbr, free_mask.to(torch.uint8).contiguous(), it)
     return b if it & 1 else a

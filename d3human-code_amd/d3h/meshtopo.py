@@ -42,7 +42,7 @@ def _raise(word, what):
 
 
 def _table_log2(items, table_log2, what):
-    lg = L.lib().d3h_topo_table_log2(L.i64(items), L.i32(table_log2))
+    lg = L.query('topo_table_log2', items, table_log2)
     if lg < 0:
         raise RuntimeError(f'd3h: {what} failed with code {lg} (bad argument): 2^{table_log2} slots cannot hold {items} keys')
     return lg
@@ -55,10 +55,9 @@ def connected_components(faces, nv):
     parent = torch.empty(nv, dtype=torch.int32, device=dev)
     label = torch.empty(nv, dtype=torch.int32, device=dev)
     err = torch.empty(1, dtype=torch.int32, device=dev)
-    lib = L.lib()
-    L.check(lib.d3h_cc_init(L.ptr(parent), L.i64(nv), L.ptr(err), L.stream()), 'cc_init')
-    L.check(lib.d3h_cc_hook(L.ptr(f), L.i32(f.dtype == torch.int64), L.i64(f.shape[0]), L.ptr(parent), L.i64(nv), L.ptr(err), L.stream()), 'cc_hook')
-    L.check(lib.d3h_cc_flatten(L.ptr(parent), L.i64(nv), L.ptr(label), L.ptr(err), L.stream()), 'cc_flatten')
+    L.call('cc_init', parent, nv, err)
+    L.call('cc_hook', f, f.dtype == torch.int64, f.shape[0], parent, nv, err)
+    L.call('cc_flatten', parent, nv, label, err)
     _raise(int(err.item()), 'connected_components')
     return label
 
@@ -92,9 +91,9 @@ def weld_representatives(v, table_log2=0):
     table = torch.empty(1 << lg, dtype=torch.int32, device=dev)
     rep = torch.empty(n, dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    lib, f64 = L.lib(), L.i32(v.dtype == torch.float64)
-    L.check(lib.d3h_weld_insert(L.ptr(v), f64, L.i64(n), L.ptr(table), L.i32(table_log2), L.ptr(err), L.stream()), 'weld_insert')
-    L.check(lib.d3h_weld_lookup(L.ptr(v), f64, L.i64(n), L.ptr(table), L.i32(table_log2), L.ptr(rep), L.ptr(err), L.stream()), 'weld_lookup')
+    f64 = v.dtype == torch.float64
+    L.call('weld_insert', v, f64, n, table, table_log2, err)
+    L.call('weld_lookup', v, f64, n, table, table_log2, rep, err)
     _raise(int(err.item()), 'weld')
     return rep
 
@@ -128,10 +127,8 @@ def open_vertex_mask(faces, nv, table_log2=0):
     counts = torch.empty(1 << lg, dtype=torch.int32, device=dev)
     mask = torch.empty(nv, dtype=torch.uint8, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    lib = L.lib()
-    L.check(lib.d3h_edge_count(L.ptr(f), L.i32(f.dtype == torch.int64), L.i64(nf), L.i64(nv), L.ptr(keys), L.ptr(counts), L.i32(table_log2), L.ptr(err),
-                               L.stream()), 'edge_count')
-    L.check(lib.d3h_open_vertex_mask(L.ptr(keys), L.ptr(counts), L.i32(lg), L.i64(nv), L.ptr(mask), L.stream()), 'open_vertex_mask')
+    L.call('edge_count', f, f.dtype == torch.int64, nf, nv, keys, counts, table_log2, err)
+    L.call('open_vertex_mask', keys, counts, lg, nv, mask)
     _raise(int(err.item()), 'open_vertices')
     return mask
 

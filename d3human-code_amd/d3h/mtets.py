@@ -62,17 +62,19 @@ class TetGrid:
         (csrc/marching_tets.hip: mt_publish); -> the sequence number to wait for.  No stream synchronisation: kernels queued after it keep the
         GPU busy while the host wakes."""
         import ctypes
-        lib = L.lib()
         if self._host is None:
             hp = ctypes.POINTER(ctypes.c_int)()
-            L.check(lib.d3h_host_flags_alloc(ctypes.byref(hp)), 'host_flags_alloc')
+            L.call('host_flags_alloc', ctypes.byref(hp))
             self._host = hp
         self._seq = (self._seq % 1000000007) + 1
-        L.check(lib.d3h_mtets_publish_sizes(L.ptr(self.counts), self._host, L.i32(self._seq), L.stream()), 'mtets_publish_sizes')
+        L.call('mtets_publish_sizes', self.counts, self._host, self._seq)
         return self._seq
 
     def _wait(self, slot, seq, first, n):
-        L.check(L.lib().d3h_host_flag_wait(self._host, L.i32(slot), L.i32(seq), L.i32(60000)), 'host_flag_wait (the GPU did not publish the sizes within 60 s)')
+        try:
+            L.call('host_flag_wait', self._host, slot, seq, 60000)
+        except L.StatusError as e:
+            raise RuntimeError(f'{e}: the GPU did not publish the sizes within 60 s') from None
         return [int(self._host[first + k]) for k in range(n)]
 
     @classmethod
@@ -90,7 +92,6 @@ class TetGrid:
 class _MTetsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, sdf, msdf, grid, msdf_sign, msdf_grad, hook=None):
-        lib = L.lib()
         dev = pos.device
         pos = pos.contiguous().float()
         sdf_shape = sdf.shape
@@ -104,8 +105,7 @@ class _MTetsFn(torch.autograd.Function):
                 # still in flight on the old one (extractions on two streams must never overlap)
                 cur.wait_stream(g._stream)
             g._stream = cur
-        L.check(lib.d3h_mtets_count(L.ptr(sdf), L.ptr(g.tets32), L.i32(g.nt), L.ptr(g.edges32), L.i32(g.ne), L.ptr(g.tet_code),
-                                    L.ptr(g.blk_e), L.ptr(g.blk_t), L.ptr(g.counts), L.stream()), 'mtets_count')
+        L.call('mtets_count', sdf, g.tets32, g.nt, g.edges32, g.ne, g.tet_code, g.blk_e, g.blk_t, g.counts)
         # the backward's zero-filled outputs (grid-sized: independent of what is extracted) are allocated and filled NOW, before the host blocks in
         # the read-back: the host is idle here, and after the read-back every launch it has to make delays the first render kernel
         # (tools/dbg/gpu_host_window.py); the backward itself sits on the launch-bound tail of the iteration
@@ -125,12 +125,9 @@ class _MTetsFn(torch.autograd.Function):
                         verts_aug=torch.empty(cp, 3, **f32), msdf_aug=torch.empty(cp, **f32), bnd_edge=torch.empty(cb, 2, **i32),
                         faces_aug=torch.empty(2 * c1 + 4 * c2, 3, **i32), faces_aug64=L.zeros((2 * c1 + 4 * c2, 3), torch.int64, dev),
                         used=torch.empty(max(cp, 1), dtype=torch.uint8, device=dev))
-            L.check(lib.d3h_mtets_emit_spec(L.ptr(pos), L.ptr(sdf), L.ptr(msdf), L.f32(msdf_sign), L.ptr(g.edges32), L.i32(g.ne), L.ptr(g.tet_edge32),
-                                            L.i32(g.nt), L.ptr(g.tet_code), L.ptr(g.blk_e), L.ptr(g.blk_t), L.ptr(g.blk_t2), L.ptr(g.counts),
-                                            L.ptr(g.edge_vid), L.i32(cw), L.i32(c1), L.i32(c2), L.ptr(spec['verts_wt']), L.ptr(spec['msdf_vert']),
-                                            L.ptr(spec['vert_edge']), L.ptr(spec['faces_wt']), L.ptr(spec['faces_wt64']), L.ptr(spec['verts_aug']),
-                                            L.ptr(spec['msdf_aug']), L.ptr(spec['bnd_edge']), L.ptr(spec['faces_aug']), L.ptr(spec['faces_aug64']),
-                                            L.ptr(spec['used']), g._host, L.i32(seq), L.stream()), 'mtets_emit_spec')
+            L.call('mtets_emit_spec', pos, sdf, msdf, msdf_sign, g.edges32, g.ne, g.tet_edge32, g.nt, g.tet_code, g.blk_e, g.blk_t, g.blk_t2,
+                   g.counts, g.edge_vid, cw, c1, c2, spec['verts_wt'], spec['msdf_vert'], spec['vert_edge'], spec['faces_wt'], spec['faces_wt64'],
+                   spec['verts_aug'], spec['msdf_aug'], spec['bnd_edge'], spec['faces_aug'], spec['faces_aug64'], spec['used'], g._host, seq)
             if hook is not None:
                 # work that needs the extracted vertices only (or tolerates the zero-padded face list), queued NOW at the capacity with the row
                 # count read on the device: the nearest-vertex search, LBS, the surface sampler and the first sweep of the eikonal chain
@@ -164,10 +161,8 @@ class _MTetsFn(torch.autograd.Function):
             vert_edge = torch.empty(pwt, 2, **i32)
             faces_wt = torch.empty(fwt, 3, **i32)
             faces_wt64 = torch.empty(fwt, 3, dtype=torch.int64, device=dev)
-            L.check(lib.d3h_mtets_emit_wt(L.ptr(pos), L.ptr(sdf), L.ptr(msdf), L.f32(msdf_sign), L.ptr(g.edges32), L.i32(g.ne),
-                                          L.ptr(g.tet_edge32), L.i32(g.nt), L.ptr(g.tet_code), L.ptr(g.blk_e), L.ptr(g.blk_t),
-                                          L.ptr(g.blk_t2), L.ptr(g.counts), L.ptr(g.edge_vid), L.ptr(verts_wt), L.ptr(msdf_vert),
-                                          L.ptr(vert_edge), L.ptr(faces_wt), L.ptr(faces_wt64), L.stream()), 'mtets_emit_wt')
+            L.call('mtets_emit_wt', pos, sdf, msdf, msdf_sign, g.edges32, g.ne, g.tet_edge32, g.nt, g.tet_code, g.blk_e, g.blk_t, g.blk_t2, g.counts,
+                   g.edge_vid, verts_wt, msdf_vert, vert_edge, faces_wt, faces_wt64)
             # The number of cut faces (six group counts, still on the device) only sizes the face list: a 1-triangle tet yields at most 2 of
             # them, a 2-triangle tet at most 4, so the list is allocated at that bound and narrowed by marching_tets() AFTER the caller had the
             # chance to queue the work that needs vertices only (nearest SMPL-X vertex + LBS of both meshes): host sync #2 then waits behind
@@ -180,10 +175,8 @@ class _MTetsFn(torch.autograd.Function):
             # those, like the surface sampler, may use the padded list before host sync #2 tells how many rows are real)
             faces_aug64 = L.zeros((faug, 3), torch.int64, dev)
             used = torch.empty(max(p, 1), dtype=torch.uint8, device=dev)
-            L.check(lib.d3h_mtets_emit_aug(L.ptr(g.tet_edge32), L.i32(g.nt), L.ptr(g.tet_code), L.ptr(g.blk_t), L.ptr(g.blk_t2),
-                                           L.ptr(g.counts), L.ptr(g.edge_vid), L.ptr(verts_wt), L.ptr(msdf_vert), L.i32(pwt), L.i32(p),
-                                           L.ptr(verts_aug), L.ptr(msdf_aug), L.ptr(bnd_edge), L.ptr(faces_aug), L.ptr(faces_aug64),
-                                           L.ptr(used), L.stream()), 'mtets_emit_aug')
+            L.call('mtets_emit_aug', g.tet_edge32, g.nt, g.tet_code, g.blk_t, g.blk_t2, g.counts, g.edge_vid, verts_wt, msdf_vert, pwt, p, verts_aug,
+                   msdf_aug, bnd_edge, faces_aug, faces_aug64, used)
         ctx.save_for_backward(pos, sdf, msdf, verts_wt, msdf_vert, vert_edge, bnd_edge, used)
         ctx.set_materialize_grads(False)       # five index outputs + whichever of the three value outputs nobody differentiates: None, not zero fills
         ctx.meta = (pwt, p, msdf_sign, msdf_grad)
@@ -196,16 +189,13 @@ class _MTetsFn(torch.autograd.Function):
     def backward(ctx, g_verts, g_msdf, g_wt, *_):
         pos, sdf, msdf, verts_wt, msdf_vert, vert_edge, bnd_edge, used = ctx.saved_tensors
         pwt, p, msdf_sign, msdf_grad = ctx.meta
-        lib = L.lib()
         z, ctx.zeros = getattr(ctx, 'zeros', None), None             # (one use: a second backward through a retained graph fills its own)
         d_pos, d_sdf, d_msdf = z if z is not None else (L.zeros_like(pos), L.zeros_like(sdf), L.zeros_like(msdf) if msdf_grad else None)
         if pwt > 0:
             scratch = torch.empty(5 * pwt, dtype=torch.float32, device=pos.device)
             c = lambda t: None if t is None else t.contiguous()
-            L.check(lib.d3h_mtets_bwd(L.ptr(c(g_verts)), L.ptr(c(g_msdf)), L.ptr(c(g_wt)), L.ptr(used), L.ptr(bnd_edge), L.ptr(vert_edge),
-                                      L.ptr(verts_wt), L.ptr(msdf_vert), L.ptr(pos), L.ptr(sdf), L.ptr(msdf), L.f32(msdf_sign),
-                                      L.i32(pwt), L.i32(p), L.ptr(scratch), L.ptr(d_pos), L.ptr(d_sdf), L.ptr(d_msdf), L.stream()),
-                    'mtets_bwd')
+            L.call('mtets_bwd', c(g_verts), c(g_msdf), c(g_wt), used, bnd_edge, vert_edge, verts_wt, msdf_vert, pos, sdf, msdf, msdf_sign, pwt, p,
+                   scratch, d_pos, d_sdf, d_msdf)
         return d_pos, d_sdf.reshape(ctx.sdf_shape), d_msdf, None, None, None, None
 
 

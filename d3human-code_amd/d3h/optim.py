@@ -176,8 +176,7 @@ class FusedAdam:
                 keep.append(gr)
             st[2] += 1
             G[i], LR[i], ST[i] = gr.data_ptr(), lr, st[2]
-        L.check(L.lib().d3h_adam_multi(c['P'], G, c['M'], c['V'], c['N'], LR, ST, c['GS'], c['LO'], c['HI'], L.i32(nt), L.f32(self.betas[0]),
-                                       L.f32(self.betas[1]), L.f32(self.eps), L.stream()), 'adam_multi')
+        L.call('adam_multi', c['P'], G, c['M'], c['V'], c['N'], LR, ST, c['GS'], c['LO'], c['HI'], nt, self.betas[0], self.betas[1], self.eps)
         del keep
         # the kernel wrote through raw pointers: tell autograd (saved-tensor checks) and every cache keyed on `_version` (weight packs,
         # the shared SDF sweep, the deformer's transforms) that the parameters changed, as an in-place torch op would have

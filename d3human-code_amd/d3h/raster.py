@@ -68,11 +68,12 @@ class _Scratch:
     bufs = {}
 
     @classmethod
-    def get(cls, name, nbytes, dev):
+    def get(cls, name, n, dev, dtype=torch.uint8):
+        """at least `n` elements of `dtype` (one dtype per name: the type of the C parameter the buffer is passed for)"""
         key = (name, str(dev))
         b = cls.bufs.get(key)
-        if b is None or b.numel() < nbytes:
-            b = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        if b is None or b.numel() < n:
+            b = torch.empty(int(n), dtype=dtype, device=dev)
             cls.bufs[key] = b
         return b
 
@@ -80,33 +81,28 @@ class _Scratch:
 class _RasterizeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, tri, H, W, nb, want_db=True, grad_db=False, prev=None, ranges=None):
-        lib = L.lib()
         pos_c = pos.contiguous().float()
         dev = pos.device
         nv, nf = pos_c.shape[1], tri.shape[0]
         rast = torch.empty(nb, H, W, 4, dtype=torch.float32, device=dev)
         # (want_db False: the caller reads no pixel derivatives -- 16 bytes per pixel the resolve pass does not write; an empty tensor comes back)
         db = torch.empty((nb, H, W, 4) if want_db else (0,), dtype=torch.float32, device=dev)
-        zbuf = _Scratch.get('zbuf', nb * H * W * 8, dev)
+        zbuf = _Scratch.get('zbuf', nb * H * W, dev, torch.int64)
         big, big_cap = None, 0
         if prev is not None or ranges is not None:
             # a peeled layer (prev: the previous layer's rast) and / or range mode (ranges: (device [nb, 2] int32, largest count)): the
             # wave-per-triangle path of d3h_rasterize_peel_fwd; the previous keys go to a scratch of their own, next to the shared z-buffer
-            pk = _Scratch.get('peel_keys', nb * H * W * 8, dev) if prev is not None else None
+            pk = _Scratch.get('peel_keys', nb * H * W, dev, torch.int64) if prev is not None else None
             rg, max_count = ranges if ranges is not None else (None, 0)
-            L.check(lib.d3h_rasterize_peel_fwd(L.ptr(pos_c), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(nf), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rg),
-                                               L.i32(max_count), L.ptr(prev), L.ptr(pk), L.ptr(zbuf), L.ptr(rast), L.ptr(db if want_db else None),
-                                               L.stream()), 'rasterize_peel_fwd')
+            L.call('rasterize_peel_fwd', pos_c, _bstride(pos_c), tri, nf, nb, H, W, rg, max_count, prev, pk, zbuf, rast, db if want_db else None)
         else:
             if nf >= BIN_MIN_TRIS:
                 # tile-binned rasteriser (csrc/raster.hip: raster_tile_kernel): header + room for BIN_PAIRS_PER_TRI (triangle, tile) pairs per
                 # triangle and frame; a render that needs more falls back on the device to the wave-per-triangle kernels -- no host read-back
                 nt = nb * (-(-W // 32)) * (-(-H // 32))
                 big_cap = min(3 * nt + 8 + BIN_PAIRS_PER_TRI * nf * nb + nf, (1 << 31) - 1)
-                big = _Scratch.get('bins', 4 * big_cap, dev).view(torch.int32)
-            L.check(lib.d3h_rasterize_fwd(L.ptr(pos_c), L.i32(nv), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(nf), L.i32(nb), L.i32(H), L.i32(W),
-                                          L.ptr(zbuf), L.ptr(big), L.i32(big_cap), L.ptr(rast), L.ptr(db if want_db else None), L.stream()),
-                    'rasterize_fwd')
+                big = _Scratch.get('bins', big_cap, dev, torch.int32)
+            L.call('rasterize_fwd', pos_c, nv, _bstride(pos_c), tri, nf, nb, H, W, zbuf, big, big_cap, rast, db if want_db else None)
         ctx.save_for_backward(pos_c, tri, rast)
         ctx.dims = (H, W, nb)
         if not (grad_db and want_db):
@@ -124,14 +120,12 @@ class _RasterizeFn(torch.autograd.Function):
         if d_pos is None:
             d_pos = L.zeros_like(pos)
         if g_db is not None:                   # the pixel derivatives were differentiated: one pass for both gradients
-            L.check(L.lib().d3h_rasterize_bwd_db(L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rast),
-                                                 L.ptr(g_rast.contiguous() if g_rast is not None else None), L.ptr(g_db.contiguous()),
-                                                 L.ptr(d_pos), L.stream()), 'rasterize_bwd_db')
+            L.call('rasterize_bwd_db', pos, _bstride(pos), tri, nb, H, W, rast, g_rast.contiguous() if g_rast is not None else None,
+                   g_db.contiguous(), d_pos)
             return (d_pos,) + (None,) * 8
         if g_rast is None:                     # nothing flowed into the barycentrics: the position gradient through them is zero
             return (d_pos,) + (None,) * 8
-        L.check(L.lib().d3h_rasterize_bwd(L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(rast),
-                                          L.ptr(g_rast.contiguous()), L.ptr(d_pos), L.stream()), 'rasterize_bwd')
+        L.call('rasterize_bwd', pos, _bstride(pos), tri, nb, H, W, rast, g_rast.contiguous(), d_pos)
         return (d_pos,) + (None,) * 8
 
 
@@ -182,7 +176,6 @@ def rasterize(pos, tri, resolution, nb=None, want_db=True, grad_db=False, prev_r
 class _InterpolateFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, attr, rast, tri, rast_db, diff_idx):
-        lib = L.lib()
         attr_c = attr.contiguous().float()
         rast_c = rast.contiguous()
         nb, H, W = rast_c.shape[:3]
@@ -191,13 +184,10 @@ class _InterpolateFn(torch.autograd.Function):
         out = torch.empty(nb, H, W, na, dtype=torch.float32, device=attr.device)
         if diff_idx is None:                   # no derivatives, or every channel in order
             out_da = torch.empty(nb, H, W, 2 * na, dtype=torch.float32, device=attr.device) if rast_db is not None else None
-            L.check(lib.d3h_interpolate_fwd(L.ptr(attr_c), L.i32(_bstride(attr_c)), L.i32(na), L.ptr(rast_c), L.ptr(tri), L.ptr(db_c),
-                                            L.i32(nb), L.i32(H), L.i32(W), L.ptr(out), L.ptr(out_da), L.stream()), 'interpolate_fwd')
+            L.call('interpolate_fwd', attr_c, _bstride(attr_c), na, rast_c, tri, db_c, nb, H, W, out, out_da)
         else:
             out_da = torch.empty(nb, H, W, 2 * diff_idx.numel(), dtype=torch.float32, device=attr.device)
-            L.check(lib.d3h_interpolate_fwd_da(L.ptr(attr_c), L.i32(_bstride(attr_c)), L.i32(na), L.ptr(rast_c), L.ptr(tri), L.ptr(db_c),
-                                               L.ptr(diff_idx), L.i32(diff_idx.numel()), L.i32(nb), L.i32(H), L.i32(W), L.ptr(out), L.ptr(out_da),
-                                               L.stream()), 'interpolate_fwd_da')
+            L.call('interpolate_fwd_da', attr_c, _bstride(attr_c), na, rast_c, tri, db_c, diff_idx, diff_idx.numel(), nb, H, W, out, out_da)
         ctx.save_for_backward(attr_c, rast_c, tri, db_c, diff_idx)
         if out_da is None:
             out_da = out.new_empty(0)
@@ -216,14 +206,12 @@ class _InterpolateFn(torch.autograd.Function):
         d_attr = L.zeros_like(attr) if need_attr else None
         d_rast = torch.empty_like(rast) if need_rast else None
         if g_da is None:
-            L.check(L.lib().d3h_interpolate_bwd(L.ptr(attr), L.i32(_bstride(attr)), L.i32(na), L.ptr(rast), L.ptr(tri), L.ptr(g_out.contiguous()),
-                                                L.i32(nb), L.i32(H), L.i32(W), L.ptr(d_attr), L.ptr(d_rast), L.stream()), 'interpolate_bwd')
+            L.call('interpolate_bwd', attr, _bstride(attr), na, rast, tri, g_out.contiguous(), nb, H, W, d_attr, d_rast)
             return d_attr, d_rast, None, None, None
         d_db = torch.empty_like(db) if need_db else None
         nidx = na if diff_idx is None else diff_idx.numel()
-        L.check(L.lib().d3h_interpolate_bwd_da(L.ptr(attr), L.i32(_bstride(attr)), L.i32(na), L.ptr(rast), L.ptr(tri), L.ptr(db), L.ptr(diff_idx),
-                                               L.i32(nidx), L.ptr(g_out.contiguous() if g_out is not None else None), L.ptr(g_da.contiguous()),
-                                               L.i32(nb), L.i32(H), L.i32(W), L.ptr(d_attr), L.ptr(d_rast), L.ptr(d_db), L.stream()), 'interpolate_bwd_da')
+        L.call('interpolate_bwd_da', attr, _bstride(attr), na, rast, tri, db, diff_idx, nidx, g_out.contiguous() if g_out is not None else None,
+               g_da.contiguous(), nb, H, W, d_attr, d_rast, d_db)
         return d_attr, d_rast, None, d_db, None
 
 
@@ -252,7 +240,6 @@ class _GBufferFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attr, face_attr, rast, tri, widths, need, want_mask, pos):
-        lib = L.lib()
         attr_c = attr.contiguous().float()
         rast_c = rast.contiguous()
         nb, H, W = rast_c.shape[:3]
@@ -266,10 +253,8 @@ class _GBufferFn(torch.autograd.Function):
         if fa is not None and fa.shape[1] == 0:            # a mesh without faces covers nothing: zeros, and no pointer to gather from
             face_out.zero_()
         mask = torch.empty(nb, H, W, 1, dtype=torch.float32, device=dev) if want_mask else None
-        L.check(lib.d3h_gbuffer_fwd(L.ptr(attr_c), L.i32(_bstride(attr_c)), L.i32(na), L.ptr(fa), L.i32(_bstride(fa) if fa is not None else 0),
-                                    L.i32(fw), L.ptr(rast_c), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(outs[0]), L.i32(w4[0]),
-                                    L.ptr(outs[1]), L.i32(w4[1]), L.ptr(outs[2]), L.i32(w4[2]), L.ptr(outs[3]), L.i32(w4[3]),
-                                    L.ptr(face_out if (fa is not None and fa.shape[1] > 0) else None), L.ptr(mask), L.stream()), 'gbuffer_fwd')
+        L.call('gbuffer_fwd', attr_c, _bstride(attr_c), na, fa, _bstride(fa) if fa is not None else 0, fw, rast_c, tri, nb, H, W, outs[0], w4[0],
+               outs[1], w4[1], outs[2], w4[2], outs[3], w4[3], face_out if (fa is not None and fa.shape[1] > 0) else None, mask)
         # `pos` (the clip positions `rast` was rasterised from; rast itself then arrives detached): the rasteriser's backward runs inside this
         # node's backward pass -- d(barycentrics) never leaves the kernel (csrc/raster.hip: gbuffer_bwd_kernel<true>)
         pos_c = pos.contiguous().float() if pos is not None else None
@@ -300,16 +285,12 @@ class _GBufferFn(torch.autograd.Function):
         fb = (fshape[1] * fshape[2] if fshape[0] > 1 else 0) if fshape is not None else 0
         if pos is not None and ctx.needs_input_grad[7]:
             d_pos = L.zeros_like(pos)
-            L.check(L.lib().d3h_gbuffer_raster_bwd(L.ptr(attr), L.i32(_bstride(attr)), L.i32(na), L.i32(fb), L.i32(fshape[2] if fshape is not None else 0),
-                                                   L.ptr(rast), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(g4[0]), L.i32(w4[0]), L.ptr(g4[1]),
-                                                   L.i32(w4[1]), L.ptr(g4[2]), L.i32(w4[2]), L.ptr(g4[3]), L.i32(w4[3]), L.ptr(g_face), L.ptr(d_attr),
-                                                   L.ptr(d_face), L.ptr(pos), L.i32(_bstride(pos)), L.ptr(d_pos), L.stream()), 'gbuffer_raster_bwd')
+            L.call('gbuffer_raster_bwd', attr, _bstride(attr), na, fb, fshape[2] if fshape is not None else 0, rast, tri, nb, H, W, g4[0], w4[0],
+                   g4[1], w4[1], g4[2], w4[2], g4[3], w4[3], g_face, d_attr, d_face, pos, _bstride(pos), d_pos)
             return d_attr, d_face, None, None, None, None, None, d_pos
         d_rast = torch.empty_like(rast) if ctx.needs_input_grad[2] else None
-        L.check(L.lib().d3h_gbuffer_bwd(L.ptr(attr), L.i32(_bstride(attr)), L.i32(na), L.i32(fb), L.i32(fshape[2] if fshape is not None else 0),
-                                        L.ptr(rast), L.ptr(tri), L.i32(nb), L.i32(H), L.i32(W), L.ptr(g4[0]), L.i32(w4[0]), L.ptr(g4[1]),
-                                        L.i32(w4[1]), L.ptr(g4[2]), L.i32(w4[2]), L.ptr(g4[3]), L.i32(w4[3]), L.ptr(g_face), L.ptr(d_attr),
-                                        L.ptr(d_face), L.ptr(d_rast), L.stream()), 'gbuffer_bwd')
+        L.call('gbuffer_bwd', attr, _bstride(attr), na, fb, fshape[2] if fshape is not None else 0, rast, tri, nb, H, W, g4[0], w4[0], g4[1], w4[1],
+               g4[2], w4[2], g4[3], w4[3], g_face, d_attr, d_face, d_rast)
         return d_attr, d_face, d_rast, None, None, None, None, None
 
 
@@ -351,9 +332,8 @@ def aux_buffers(clip, rast, db, tri, gb_pos, view_pos, want_z=True, want_depth=T
             vp = view_pos.detach().reshape(-1, 3).contiguous().float()
             vstride = 3 if vp.shape[0] > 1 else 0
             assert vp.shape[0] in (1, nb)
-        L.check(L.lib().d3h_aux_buffers_fwd(L.ptr(clip_c), L.i32(_bstride(clip_c) if want_z else 0), L.ptr(rast.contiguous()),
-                                            L.ptr(db.contiguous()) if want_z else None, L.ptr(tri.contiguous()) if want_z else None, L.ptr(gp), L.ptr(vp),
-                                            L.i32(vstride), L.i32(nb), L.i32(H), L.i32(W), L.ptr(z), L.ptr(dep), L.ptr(inv), L.stream()), 'aux_buffers_fwd')
+        L.call('aux_buffers_fwd', clip_c, _bstride(clip_c) if want_z else 0, rast.contiguous(), db.contiguous() if want_z else None,
+               tri.contiguous() if want_z else None, gp, vp, vstride, nb, H, W, z, dep, inv)
     return z, dep, inv
 
 
@@ -368,9 +348,9 @@ def _hash_for(tri):
     nf = tri.shape[0]
     cap = _hash_cap(nf)
     dev = tri.device
-    kv = _Scratch.get('aa_keys_vals', cap * 16, dev)          # keys [cap] uint64 | vals [2 cap] int32, contiguous: the library fills both at once
-    keys, vals = kv[:cap * 8], kv[cap * 8:cap * 16]
-    L.check(L.lib().d3h_antialias_hash(L.ptr(tri), L.i32(nf), L.ptr(keys), L.ptr(vals), L.i32(cap), L.stream()), 'antialias_hash')
+    kv = _Scratch.get('aa_keys_vals', cap * 2, dev, torch.int64)          # keys [cap] uint64 | vals [2 cap] int32, contiguous: the library fills both at once
+    keys, vals = kv[:cap], kv[cap:cap * 2].view(torch.int32)
+    L.call('antialias_hash', tri, nf, keys, vals, cap)
     return keys, vals, cap
 
 
@@ -383,9 +363,9 @@ class TopologyHash:
         tri = tri.contiguous()
         nf = tri.shape[0]
         cap = _hash_cap(nf)
-        kv = torch.empty(cap * 16, dtype=torch.uint8, device=tri.device)          # one allocation: keys | vals, as _hash_for's
-        self.keys, self.vals, self.cap, self.nf = kv[:cap * 8], kv[cap * 8:], cap, nf
-        L.check(L.lib().d3h_antialias_hash(L.ptr(tri), L.i32(nf), L.ptr(self.keys), L.ptr(self.vals), L.i32(cap), L.stream()), 'antialias_hash')
+        kv = torch.empty(cap * 2, dtype=torch.int64, device=tri.device)          # one allocation: keys | vals, as _hash_for's
+        self.keys, self.vals, self.cap, self.nf = kv[:cap], kv[cap:].view(torch.int32), cap, nf
+        L.call('antialias_hash', tri, nf, self.keys, self.vals, cap)
 
 
 def antialias_construct_topology_hash(tri):
@@ -401,21 +381,18 @@ def _edge_flags(pos_c, tri, nb, H, W, topology_hash=None):
     else:
         keys, vals, cap = topology_hash.keys, topology_hash.vals, topology_hash.cap
     flags = torch.empty(nb, max(nf, 1), dtype=torch.uint8, device=pos_c.device)
-    L.check(L.lib().d3h_antialias_flags(L.ptr(pos_c), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(nf), L.i32(nb), L.ptr(keys), L.ptr(vals), L.i32(cap),
-                                        L.i32(H), L.i32(W), L.ptr(flags), L.stream()), 'antialias_flags')
+    L.call('antialias_flags', pos_c, _bstride(pos_c), tri, nf, nb, keys, vals, cap, H, W, flags)
     return flags
 
 
 class _AntialiasFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0):
-        lib = L.lib()
         color_c, rast_c, pos_c = color.contiguous().float(), rast.contiguous(), pos.contiguous().float()
         nb, H, W, C = color_c.shape
         flags = _edge_flags(pos_c, tri, nb, H, W, topology_hash)        # per render; the backward reuses them (nb x nf bytes)
         out = torch.empty_like(color_c)
-        L.check(lib.d3h_antialias_fwd(L.ptr(color_c), L.ptr(rast_c), L.ptr(pos_c), L.i32(_bstride(pos_c)), L.ptr(tri), L.i32(tri.shape[0]),
-                                      L.ptr(flags), L.i32(nb), L.i32(H), L.i32(W), L.i32(C), L.ptr(out), L.stream()), 'antialias_fwd')
+        L.call('antialias_fwd', color_c, rast_c, pos_c, _bstride(pos_c), tri, tri.shape[0], flags, nb, H, W, C, out)
         ctx.save_for_backward(color_c, rast_c, pos_c, tri, flags)
         ctx.boost = float(pos_gradient_boost)
         return out
@@ -426,9 +403,7 @@ class _AntialiasFn(torch.autograd.Function):
         nb, H, W, C = color.shape
         g_color = torch.empty_like(color)
         d_pos = L.zeros_like(pos) if ctx.needs_input_grad[2] else None
-        L.check(L.lib().d3h_antialias_bwd(L.ptr(color), L.ptr(rast), L.ptr(pos), L.i32(_bstride(pos)), L.ptr(tri), L.i32(tri.shape[0]), L.ptr(flags),
-                                          L.i32(nb), L.i32(H), L.i32(W), L.i32(C), L.ptr(g_out.contiguous()), L.ptr(g_color), L.ptr(d_pos),
-                                          L.stream()), 'antialias_bwd')
+        L.call('antialias_bwd', color, rast, pos, _bstride(pos), tri, tri.shape[0], flags, nb, H, W, C, g_out.contiguous(), g_color, d_pos)
         if d_pos is not None and ctx.boost != 1.0:
             d_pos.mul_(ctx.boost)
         return g_color, None, d_pos, None, None, None
@@ -457,8 +432,7 @@ class _TextureFn(torch.autograd.Function):
         TH, TW, C = tex_c.shape[1:]
         out = torch.empty(nb, H, W, C, dtype=torch.float32, device=tex.device)
         bs = 0 if tex_c.shape[0] == 1 else TH * TW * C
-        L.check(L.lib().d3h_texture_fwd(L.ptr(tex_c), L.i32(bs), L.i32(TH), L.i32(TW), L.i32(C), L.ptr(uv_c), L.i32(nb), L.i32(H), L.i32(W),
-                                        L.ptr(out), L.stream()), 'texture_fwd')
+        L.call('texture_fwd', tex_c, bs, TH, TW, C, uv_c, nb, H, W, out)
         ctx.save_for_backward(uv_c)
         ctx.tshape = tuple(tex_c.shape)
         return out
@@ -470,8 +444,7 @@ class _TextureFn(torch.autograd.Function):
         B, TH, TW, C = ctx.tshape
         d_tex = L.zeros(ctx.tshape, torch.float32, uv.device)
         bs = 0 if B == 1 else TH * TW * C
-        L.check(L.lib().d3h_texture_bwd(L.i32(bs), L.i32(TH), L.i32(TW), L.i32(C), L.ptr(uv), L.i32(nb), L.i32(H), L.i32(W),
-                                        L.ptr(g_out.contiguous()), L.ptr(d_tex), L.stream()), 'texture_bwd')
+        L.call('texture_bwd', bs, TH, TW, C, uv, nb, H, W, g_out.contiguous(), d_tex)
         return d_tex, None
 
 

@@ -19,7 +19,7 @@ BUILDS = 0
 
 def _layout(F):
     sizes = (ctypes.c_int64 * 4)()
-    L.check(L.lib().d3h_bvh_layout(L.i64(F), sizes), 'bvh_layout')
+    L.call('bvh_layout', F, sizes)
     return [int(v) for v in sizes]
 
 
@@ -49,11 +49,9 @@ class Bvh:
         self.nodes = torch.empty(n_nodes, dtype=torch.float32, device=dev)
         self.tri9 = torch.empty(n_tri, dtype=torch.float32, device=dev)
         work = torch.empty(n_work, dtype=torch.int32, device=dev)
-        lib = L.lib()
 
         def phase(p, k):
-            L.check(lib.d3h_bvh_build(L.i32(p), L.ptr(verts), L.i64(V), L.ptr(tris), L.i32(wide), L.i64(F), L.ptr(cbounds), L.ptr(k), L.ptr(self.nodes),
-                                      L.ptr(self.tri9), L.ptr(work), L.stream()), 'bvh_build')
+            L.call('bvh_build', p, verts, V, tris, wide, F, cbounds, k, self.nodes, self.tri9, work)
         phase(0, keys)
         phase(1, torch.sort(keys).values.contiguous())
 
@@ -64,6 +62,5 @@ class Bvh:
         o = origins.detach().reshape(-1, 3).float().contiguous()
         d = dirs.detach().reshape(-1, 3).float().contiguous()
         out = torch.empty(o.shape[0], dtype=torch.uint8, device=o.device)
-        L.check(L.lib().d3h_bvh_occluded(L.ptr(self.nodes), L.ptr(self.tri9), L.i64(self.F), L.ptr(o), L.ptr(d), L.i64(o.shape[0]), L.f32(tmin), L.f32(tmax),
-                                         L.ptr(out), L.stream()), 'bvh_occluded')
+        L.call('bvh_occluded', self.nodes, self.tri9, self.F, o, d, o.shape[0], tmin, tmax, out)
         return out.bool().reshape(shape)

@@ -43,25 +43,23 @@ def check_shape(sd, prefix='net.'):
 def pack_weights(sd, prefix='net.', out=None):
     """state_dict-like {net.i.weight, net.i.bias} -> packed fragment-order buffer (see csrc/sdf_mlp_layout.h)."""
     check_shape(sd, prefix)
-    lib = L.lib()
     g = lambda k: sd[prefix + k].detach().contiguous().float()
     wh = torch.stack([g(f'{i}.weight') for i in HIDDEN_KEYS]).contiguous()
     bh = torch.stack([g(f'{i}.bias') for i in HIDDEN_KEYS]).contiguous()
     keep = [g('0.weight'), g('0.bias'), wh, bh, g('8.weight'), g('8.bias'), g('14.weight'), g('14.bias')]
     if out is None:
-        out = torch.empty(lib.d3h_sdf_mlp_wpack_floats(), dtype=torch.float32, device=keep[0].device)
-    L.check(lib.d3h_sdf_mlp_pack(*[L.ptr(t) for t in keep], L.ptr(out), L.stream()), 'sdf_mlp_pack')
+        out = torch.empty(L.query('sdf_mlp_wpack_floats'), dtype=torch.float32, device=keep[0].device)
+    L.call('sdf_mlp_pack', *keep, out)
     return out
 
 
 def forward(x, wpack, deform=None, disp=0.0, save=False, want_xdef=False, max_cus=0, wp3=None):
     """sdf[n] (and optionally the saved activations / deformed points) for points x[n,3].  max_cus: a launch of fewer than 1024 point
     tiles uses at most this many CUs (0 = the chip), so that another stream's kernels find free ones next to it."""
-    lib = L.lib()
     x = x.contiguous().float()
     n = x.shape[0]
     sdf = torch.empty(n, dtype=torch.float32, device=x.device)
-    act = torch.empty(lib.d3h_sdf_mlp_act_floats(n), dtype=torch.float32, device=x.device) if save else None
+    act = torch.empty(L.query('sdf_mlp_act_floats', n), dtype=torch.float32, device=x.device) if save else None
     xdef = torch.empty(n, 3, dtype=torch.float32, device=x.device) if want_xdef else None
     d = deform.contiguous().float() if deform is not None else None
     ev = None
@@ -69,14 +67,11 @@ def forward(x, wpack, deform=None, disp=0.0, save=False, want_xdef=False, max_cu
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
     if wp3 is not None and getattr(wp3, 'd3h_planes', 3) == 2:       # a pack of pack_weights_h2: the fp16 x 2 sweep
-        L.check(lib.d3h_sdf_mlp_fwd_h2(L.ptr(x), L.ptr(d), L.f32(disp), L.ptr(wp3), L.ptr(sdf), L.ptr(xdef), L.ptr(act), L.i64(n),
-                                       L.i32(max_cus), L.stream()), 'sdf_mlp_fwd_h2')
+        L.call('sdf_mlp_fwd_h2', x, d, disp, wp3, sdf, xdef, act, n, max_cus)
     elif wp3 is not None:       # same outputs on the bf16 matrix pipe (wpack3 of the same weights: pack_weights3 / PackedWeights.wp3)
-        L.check(lib.d3h_sdf_mlp_fwd_x3(L.ptr(x), L.ptr(d), L.f32(disp), L.ptr(wp3), L.ptr(sdf), L.ptr(xdef), L.ptr(act), L.i64(n),
-                                       L.i32(max_cus), L.stream()), 'sdf_mlp_fwd_x3')
+        L.call('sdf_mlp_fwd_x3', x, d, disp, wp3, sdf, xdef, act, n, max_cus)
     else:
-        L.check(lib.d3h_sdf_mlp_fwd(L.ptr(x), L.ptr(d), L.f32(disp), L.ptr(wpack), L.ptr(sdf), L.ptr(xdef), L.ptr(act), L.i64(n),
-                                    L.i32(max_cus), L.stream()), 'sdf_mlp_fwd')
+        L.call('sdf_mlp_fwd', x, d, disp, wpack, sdf, xdef, act, n, max_cus)
     if ev is not None:
         ev[1].record()
         TIMING.append((ev[0], ev[1], n))
@@ -88,41 +83,38 @@ def forward(x, wpack, deform=None, disp=0.0, save=False, want_xdef=False, max_cu
 def pack_weights3(sd, prefix='net.', out=None):
     """the bf16 x 3 pack of the same weights for forward(..., wp3=) (csrc/sdf_mlp_x3.h)"""
     check_shape(sd, prefix)
-    lib = L.lib()
     g = lambda k: sd[prefix + k].detach().contiguous().float()
     wh = torch.stack([g(f'{i}.weight') for i in HIDDEN_KEYS]).contiguous()
     bh = torch.stack([g(f'{i}.bias') for i in HIDDEN_KEYS]).contiguous()
     keep = [g('0.weight'), g('0.bias'), wh, bh, g('8.weight'), g('8.bias'), g('14.weight'), g('14.bias')]
     if out is None:
-        out = torch.empty(lib.d3h_sdf_mlp_wpack3_dwords(), dtype=torch.int32, device=keep[0].device)
-    L.check(lib.d3h_sdf_mlp_pack3(*[L.ptr(t) for t in keep], L.ptr(out), L.stream()), 'sdf_mlp_pack3')
+        out = torch.empty(L.query('sdf_mlp_wpack3_dwords'), dtype=torch.int32, device=keep[0].device)
+    L.call('sdf_mlp_pack3', *keep, out)
     return out
 
 
 def pack_weights_h2(sd, prefix='net.', out=None):
     """the fp16 x 2 pack of the same weights for forward(..., wp3=<this>) (csrc/sdf_mlp_x3.h "h2"); the result is tagged `d3h_planes = 2`"""
     check_shape(sd, prefix)
-    lib = L.lib()
     g = lambda k: sd[prefix + k].detach().contiguous().float()
     wh = torch.stack([g(f'{i}.weight') for i in HIDDEN_KEYS]).contiguous()
     bh = torch.stack([g(f'{i}.bias') for i in HIDDEN_KEYS]).contiguous()
     keep = [g('0.weight'), g('0.bias'), wh, bh, g('8.weight'), g('8.bias'), g('14.weight'), g('14.bias')]
     if out is None:
-        out = torch.empty(lib.d3h_sdf_mlp_wpackh2_dwords(), dtype=torch.int32, device=keep[0].device)
-    L.check(lib.d3h_sdf_mlp_pack_h2(*[L.ptr(t) for t in keep], L.ptr(out), L.stream()), 'sdf_mlp_pack_h2')
+        out = torch.empty(L.query('sdf_mlp_wpackh2_dwords'), dtype=torch.int32, device=keep[0].device)
+    L.call('sdf_mlp_pack_h2', *keep, out)
     out.d3h_planes = 2
     return out
 
 
 def pack_weights_t(sd, prefix='net.', out=None):
     """transposed fragment-order pack for the backward-data kernel"""
-    lib = L.lib()
     g = lambda k: sd[prefix + k].detach().contiguous().float()
     wh = torch.stack([g(f'{i}.weight') for i in HIDDEN_KEYS]).contiguous()
     keep = [g('0.weight'), wh, g('8.weight')]
     if out is None:
-        out = torch.empty(lib.d3h_sdf_mlp_wpackt_floats(), dtype=torch.float32, device=keep[0].device)
-    L.check(lib.d3h_sdf_mlp_pack_t(*[L.ptr(t) for t in keep], L.ptr(out), L.stream()), 'sdf_mlp_pack_t')
+        out = torch.empty(L.query('sdf_mlp_wpackt_floats'), dtype=torch.float32, device=keep[0].device)
+    L.call('sdf_mlp_pack_t', *keep, out)
     return out
 
 
@@ -176,13 +168,12 @@ def arena_views(flat):
 
 def pack_weights_t_h2(sd, prefix='net.', out=None):
     """the fp16 x 2 transposed pack for the data-backward sweeps (csrc/sdf_mlp_x3.h "h2"); tagged `d3h_planes = 2`"""
-    lib = L.lib()
     g = lambda k: sd[prefix + k].detach().contiguous().float()
     wh = torch.stack([g(f'{i}.weight') for i in HIDDEN_KEYS]).contiguous()
     keep = [g('0.weight'), wh, g('8.weight')]
     if out is None:
-        out = torch.empty(lib.d3h_sdf_mlp_wpackth2_dwords(), dtype=torch.int32, device=keep[0].device)
-    L.check(lib.d3h_sdf_mlp_pack_t_h2(*[L.ptr(t) for t in keep], L.ptr(out), L.stream()), 'sdf_mlp_pack_t_h2')
+        out = torch.empty(L.query('sdf_mlp_wpackth2_dwords'), dtype=torch.int32, device=keep[0].device)
+    L.call('sdf_mlp_pack_t_h2', *keep, out)
     out.d3h_planes = 2
     return out
 
@@ -193,13 +184,12 @@ def _planes(t):
 
 def pack_weights_t3(sd, prefix='net.', out=None):
     """the bf16 x 3 transposed pack for the data-backward sweeps (csrc/sdf_mlp_x3.h)"""
-    lib = L.lib()
     g = lambda k: sd[prefix + k].detach().contiguous().float()
     wh = torch.stack([g(f'{i}.weight') for i in HIDDEN_KEYS]).contiguous()
     keep = [g('0.weight'), wh, g('8.weight')]
     if out is None:
-        out = torch.empty(lib.d3h_sdf_mlp_wpackt3_dwords(), dtype=torch.int32, device=keep[0].device)
-    L.check(lib.d3h_sdf_mlp_pack_t3(*[L.ptr(t) for t in keep], L.ptr(out), L.stream()), 'sdf_mlp_pack_t3')
+        out = torch.empty(L.query('sdf_mlp_wpackt3_dwords'), dtype=torch.int32, device=keep[0].device)
+    L.call('sdf_mlp_pack_t3', *keep, out)
     return out
 
 
@@ -211,39 +201,34 @@ class PackedWeights:
     def __init__(self, params):
         self.key = tuple((p.data_ptr(), p._version) for p in params)
         self.flat = _FlatParams.apply(*params)                  # differentiable: both consumers' gradients meet here
-        lib = L.lib()
         w0, b0, wh, bh, w8, b8, w14, b14 = arena_views(self.flat.detach())
         self.wp = self.wpt = self.wp3 = self.wpt3 = self.wph = None
         dbg = os.environ.get('D3H_X3_DEBUG_PARTS')      # diagnostic: e.g. "fwd,eik" keeps only those sweeps on the bf16 pipe (both packs built)
         if X3 and dbg is not None:
-            self.wp = torch.empty(lib.d3h_sdf_mlp_wpack_floats(), dtype=torch.float32, device=w0.device)
-            L.check(lib.d3h_sdf_mlp_pack(L.ptr(w0), L.ptr(b0), L.ptr(wh), L.ptr(bh), L.ptr(w8), L.ptr(b8), L.ptr(w14), L.ptr(b14), L.ptr(self.wp),
-                                         L.stream()), 'sdf_mlp_pack')
-            self.wpt = torch.empty(lib.d3h_sdf_mlp_wpackt_floats(), dtype=torch.float32, device=w0.device)
-            L.check(lib.d3h_sdf_mlp_pack_t(L.ptr(w0), L.ptr(wh), L.ptr(w8), L.ptr(self.wpt), L.stream()), 'sdf_mlp_pack_t')
+            self.wp = torch.empty(L.query('sdf_mlp_wpack_floats'), dtype=torch.float32, device=w0.device)
+            L.call('sdf_mlp_pack', w0, b0, wh, bh, w8, b8, w14, b14, self.wp)
+            self.wpt = torch.empty(L.query('sdf_mlp_wpackt_floats'), dtype=torch.float32, device=w0.device)
+            L.call('sdf_mlp_pack_t', w0, wh, w8, self.wpt)
         if X3:       # the split-plane packs carry everything the sweeps need (biases and head included): the f32 packs are not built
             if not (H2 and H2_JVP) or dbg is not None:          # (with every forward-type sweep on the fp16 x 2 pack nobody reads the bf16 x 3 one)
-                self.wp3 = torch.empty(lib.d3h_sdf_mlp_wpack3_dwords(), dtype=torch.int32, device=w0.device)
-                L.check(lib.d3h_sdf_mlp_pack3(L.ptr(w0), L.ptr(b0), L.ptr(wh), L.ptr(bh), L.ptr(w8), L.ptr(b8), L.ptr(w14), L.ptr(b14), L.ptr(self.wp3),
-                                              L.stream()), 'sdf_mlp_pack3')
+                self.wp3 = torch.empty(L.query('sdf_mlp_wpack3_dwords'), dtype=torch.int32, device=w0.device)
+                L.call('sdf_mlp_pack3', w0, b0, wh, bh, w8, b8, w14, b14, self.wp3)
             if H2 and H2_BWD:      # the data-backward sweeps on the fp16 x 2 split too (operands scaled per launch, csrc/sdf_mlp_x3.h: h2_grad_scale)
-                self.wpt3 = torch.empty(lib.d3h_sdf_mlp_wpackth2_dwords(), dtype=torch.int32, device=w0.device)
-                L.check(lib.d3h_sdf_mlp_pack_t_h2(L.ptr(w0), L.ptr(wh), L.ptr(w8), L.ptr(self.wpt3), L.stream()), 'sdf_mlp_pack_t_h2')
+                self.wpt3 = torch.empty(L.query('sdf_mlp_wpackth2_dwords'), dtype=torch.int32, device=w0.device)
+                L.call('sdf_mlp_pack_t_h2', w0, wh, w8, self.wpt3)
                 self.wpt3.d3h_planes = 2
             else:
-                self.wpt3 = torch.empty(lib.d3h_sdf_mlp_wpackt3_dwords(), dtype=torch.int32, device=w0.device)
-                L.check(lib.d3h_sdf_mlp_pack_t3(L.ptr(w0), L.ptr(wh), L.ptr(w8), L.ptr(self.wpt3), L.stream()), 'sdf_mlp_pack_t3')
+                self.wpt3 = torch.empty(L.query('sdf_mlp_wpackt3_dwords'), dtype=torch.int32, device=w0.device)
+                L.call('sdf_mlp_pack_t3', w0, wh, w8, self.wpt3)
             if H2:      # the forward-type sweeps read this one (fp16 x 2); wp3 stays for the tangent sweep
-                self.wph = torch.empty(lib.d3h_sdf_mlp_wpackh2_dwords(), dtype=torch.int32, device=w0.device)
-                L.check(lib.d3h_sdf_mlp_pack_h2(L.ptr(w0), L.ptr(b0), L.ptr(wh), L.ptr(bh), L.ptr(w8), L.ptr(b8), L.ptr(w14), L.ptr(b14), L.ptr(self.wph),
-                                                L.stream()), 'sdf_mlp_pack_h2')
+                self.wph = torch.empty(L.query('sdf_mlp_wpackh2_dwords'), dtype=torch.int32, device=w0.device)
+                L.call('sdf_mlp_pack_h2', w0, b0, wh, bh, w8, b8, w14, b14, self.wph)
                 self.wph.d3h_planes = 2
         else:
-            self.wp = torch.empty(lib.d3h_sdf_mlp_wpack_floats(), dtype=torch.float32, device=w0.device)
-            L.check(lib.d3h_sdf_mlp_pack(L.ptr(w0), L.ptr(b0), L.ptr(wh), L.ptr(bh), L.ptr(w8), L.ptr(b8), L.ptr(w14), L.ptr(b14), L.ptr(self.wp),
-                                         L.stream()), 'sdf_mlp_pack')
-            self.wpt = torch.empty(lib.d3h_sdf_mlp_wpackt_floats(), dtype=torch.float32, device=w0.device)
-            L.check(lib.d3h_sdf_mlp_pack_t(L.ptr(w0), L.ptr(wh), L.ptr(w8), L.ptr(self.wpt), L.stream()), 'sdf_mlp_pack_t')
+            self.wp = torch.empty(L.query('sdf_mlp_wpack_floats'), dtype=torch.float32, device=w0.device)
+            L.call('sdf_mlp_pack', w0, b0, wh, bh, w8, b8, w14, b14, self.wp)
+            self.wpt = torch.empty(L.query('sdf_mlp_wpackt_floats'), dtype=torch.float32, device=w0.device)
+            L.call('sdf_mlp_pack_t', w0, wh, w8, self.wpt)
         self.w14 = w14
 
     def valid_for(self, params):
@@ -289,7 +274,6 @@ def prepare_backward(sdf, edges32):
     if not PREPARE or st is None or st[0] != sdf.data_ptr() or st[1].get('done') or edges32 is None:
         return
     state = st[1]
-    lib = L.lib()
     n, dev = state['n'], sdf.device
     if sdf.numel() != n:
         return
@@ -307,11 +291,10 @@ def prepare_backward(sdf, edges32):
     with (L.use_stream(side) if side is not None else contextlib.nullcontext()):
         marks = torch.zeros(n, dtype=torch.float32, device=dev)
         sums = torch.empty(2, dtype=torch.float32, device=dev)
-        act = torch.empty(int(lib.d3h_sdf_mlp_act_floats(n)), dtype=torch.float32, device=dev)
-        tiles = torch.empty(int(lib.d3h_sdf_mlp_bwd_scratch_ints(n)), dtype=torch.int32, device=dev)
-        L.check(lib.d3h_sdf_reg_fwd(L.ptr(sd), L.ptr(e32), L.i32(e32.shape[0]), L.ptr(sums), L.ptr(marks), L.stream()), 'sdf_reg_fwd (marks)')
-        L.check(lib.d3h_sdf_mlp_bwd_prepare(L.ptr(x), L.ptr(deform), L.f32(disp), L.ptr(marks), L.i64(n), L.ptr(tiles), L.ptr(wp3_rec),
-                                            L.i32(_planes(wp3_rec)), L.ptr(act), L.stream()), 'sdf_mlp_bwd_prepare')
+        act = torch.empty(L.query('sdf_mlp_act_floats', n), dtype=torch.float32, device=dev)
+        tiles = torch.empty(L.query('sdf_mlp_bwd_scratch_ints', n), dtype=torch.int32, device=dev)
+        L.call('sdf_reg_fwd', sd, e32, e32.shape[0], sums, marks)
+        L.call('sdf_mlp_bwd_prepare', x, deform, disp, marks, n, tiles, wp3_rec, _planes(wp3_rec), act)
         ev = None
         if side is not None:
             ev = torch.cuda.Event()
@@ -362,7 +345,6 @@ class _SDFMLPFn(torch.autograd.Function):
         x, deform, act = ctx.saved_tensors
         if not ctx.has_deform:
             deform = None
-        lib = L.lib()
         wpt, w7, wpt3, wp3_rec = ctx.wpt, ctx.w14, ctx.wpt3, ctx.wp3_rec
         ctx.wpt = ctx.w14 = ctx.wpt3 = ctx.wp3_rec = None
         rows, leaf = ctx.rows, ctx.deform_leaf
@@ -386,7 +368,7 @@ class _SDFMLPFn(torch.autograd.Function):
                 for t in (act, tiles):
                     t.record_stream(_cur_stream())
         elif wp3_rec is not None:             # scratch for the recomputed activations (written at the visited tiles' own positions only)
-            act = torch.empty(int(lib.d3h_sdf_mlp_act_floats(n)), dtype=torch.float32, device=dev)
+            act = torch.empty(L.query('sdf_mlp_act_floats', n), dtype=torch.float32, device=dev)
         dz = torch.empty_like(act)
         dx = torch.empty(n, 3, dtype=torch.float32, device=dev)
         arena = L.zeros(ARENA_FLOATS, torch.float32, dev)          # (carved from the zero slab: no fill launch); returned as d(flat)
@@ -395,11 +377,9 @@ class _SDFMLPFn(torch.autograd.Function):
         # active-tile list: the backward only visits 16-point tiles with a non-zero upstream gradient (csrc/sdf_mlp_bwd.hip, section 0)
         # scratch of the sparse backward: the position-tile list, or -- compact form, when the activations are recomputed -- the gathered problem
         if tiles is None:
-            tiles = torch.empty(int(lib.d3h_sdf_mlp_bwd_scratch_ints(n)), dtype=torch.int32, device=dev) if SPARSE_BACKWARD else None
-        L.check(lib.d3h_sdf_mlp_bwd(L.ptr(xc), L.ptr(dfm), L.f32(ctx.disp), L.ptr(g), L.ptr(w7), L.ptr(wpt), L.ptr(wpt3), L.ptr(act), L.ptr(dz),
-                                    L.i64(n), L.ptr(dx), L.ptr(dw0), L.ptr(db0), L.ptr(dwh), L.ptr(dbh), L.ptr(dw4), L.ptr(db4),
-                                    L.ptr(dw7), L.ptr(db7), L.ptr(tiles), L.ptr(wp3_rec), L.i32(_planes(wp3_rec)), L.i32(_planes(wpt3)),
-                                    L.i32(1 if prepared else 0), L.stream()), 'sdf_mlp_bwd')
+            tiles = torch.empty(L.query('sdf_mlp_bwd_scratch_ints', n), dtype=torch.int32, device=dev) if SPARSE_BACKWARD else None
+        L.call('sdf_mlp_bwd', xc, dfm, ctx.disp, g, w7, wpt, wpt3, act, dz, n, dx, dw0, db0, dwh, dbh, dw4, db4, dw7, db7, tiles, wp3_rec,
+               _planes(wp3_rec), _planes(wpt3), 1 if prepared else 0)
         d_deform = None
         if deform is not None and ctx.needs_input_grad[1]:
             # frame-parallel step: into the gradient's slice of the all-reduce arena (first contribution: written; later: added in place)
@@ -426,7 +406,6 @@ class _SDFGradFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *params):
-        lib = L.lib()
         sd = {k: p for k, p in zip(_PARAM_ORDER, params)}
         wp = pack_weights(sd, prefix='')
         wpt = pack_weights_t(sd, prefix='')
@@ -438,13 +417,12 @@ class _SDFGradFn(torch.autograd.Function):
         dz = torch.empty_like(act)
         g = torch.empty(n, 3, dtype=torch.float32, device=xc.device)
         w7 = sd['14.weight'].detach().contiguous().float()
-        L.check(lib.d3h_sdf_mlp_grad_x(L.ptr(xc), L.ptr(w7), L.ptr(wpt), L.ptr(wpt3), L.i32(_planes(wpt3)), L.ptr(act), L.ptr(dz), L.i64(n), L.ptr(g), L.i32(0), L.stream()), 'sdf_mlp_grad_x')
+        L.call('sdf_mlp_grad_x', xc, w7, wpt, wpt3, _planes(wpt3), act, dz, n, g, 0)
         ctx.bufs = (xc, wp, wpt, wp3, wpt3, act, dz)
         return g
 
     @staticmethod
     def backward(ctx, u):
-        lib = L.lib()
         xc, wp, wpt, wp3, wpt3, act, dz = ctx.bufs
         ctx.bufs = None
         n = xc.shape[0]
@@ -453,9 +431,8 @@ class _SDFGradFn(torch.autograd.Function):
         tb, eb = torch.empty_like(act), torch.empty_like(act)
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         dw0, db0, dwh, dbh, dw4, db4, dw7 = z(256, 39), z(256), z(5, 256, 256), z(5, 256), z(256, 295), z(256), z(1, 256)
-        L.check(lib.d3h_sdf_mlp_eik_bwd(L.ptr(xc), L.ptr(u), L.ptr(wp), L.ptr(wpt), L.ptr(wp3), L.i32(_planes(wp3)), L.ptr(wpt3), L.i32(_planes(wpt3)), L.f32(0.0), L.ptr(act), L.ptr(dz), L.ptr(tb), L.ptr(eb), L.i64(n),
-                                        L.ptr(dw0), L.ptr(db0), L.ptr(dwh), L.ptr(dbh), L.ptr(dw4), L.ptr(db4), L.ptr(dw7), L.i32(0), L.stream()),
-                'sdf_mlp_eik_bwd')
+        L.call('sdf_mlp_eik_bwd', xc, u, wp, wpt, wp3, _planes(wp3), wpt3, _planes(wpt3), 0.0, act, dz, tb, eb, n, dw0, db0, dwh, dbh, dw4, db4, dw7,
+               0)
         grads = [dw0, db0, dwh[0], dbh[0], dwh[1], dbh[1], dwh[2], dbh[2], dw4, db4, dwh[3], dbh[3], dwh[4], dbh[4], dw7, None]
         return (None, *grads)
 
@@ -476,7 +453,6 @@ class _EikonalLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, coeff, pk, flat, begun, max_cus):
-        lib = L.lib()
         wp, wpt = pk.wp, pk.wpt
         if begun is not None:               # eikonal_begin() already queued the forward sweep on these points with these weights
             xc, act = begun
@@ -489,11 +465,11 @@ class _EikonalLossFn(torch.autograd.Function):
         g = torch.empty(n, 3, dtype=torch.float32, device=dev)
         w7 = pk.w14
         wpt3 = _part(pk.wpt3, 'eik')
-        L.check(lib.d3h_sdf_mlp_grad_x(L.ptr(xc), L.ptr(w7), L.ptr(wpt), L.ptr(wpt3), L.i32(_planes(wpt3)), L.ptr(act), L.ptr(dz), L.i64(n), L.ptr(g), L.i32(max_cus), L.stream()), 'sdf_mlp_grad_x')
+        L.call('sdf_mlp_grad_x', xc, w7, wpt, wpt3, _planes(wpt3), act, dz, n, g, max_cus)
         need = flat.requires_grad
         s = torch.empty(1, dtype=torch.float32, device=dev)
         u = torch.empty_like(g) if need else None
-        L.check(lib.d3h_eikonal_loss(L.ptr(g), L.i64(n), L.f32(float(coeff) / max(n, 1)), L.ptr(s), L.ptr(u), L.stream()), 'eikonal_loss')
+        L.call('eikonal_loss', g, n, float(coeff) / max(n, 1), s, u)
         ret = s[0] * (float(coeff) / max(n, 1))
         # The loss value exists now; the eager second-order sweeps below only produce parameter gradients.  A caller that runs this op
         # on a side stream can wait for LOSS_READY instead of the whole stream: the sweeps (MFMA-bound, ~2.3 ms at 5 10^4 points) then
@@ -519,10 +495,8 @@ class _EikonalLossFn(torch.autograd.Function):
             arena = L.zeros(ARENA_FLOATS, torch.float32, dev)
             dw0, db0, dwh, dbh, dw4, db4, dw7, _ = arena_views(arena)
             wpj = _part(pk.wph if (pk.wph is not None and H2_JVP) else pk.wp3, 'eik')          # the tangent sweep's pack: fp16 x 2 when built
-            L.check(lib.d3h_sdf_mlp_eik_bwd(L.ptr(xc), L.ptr(u), L.ptr(wp), L.ptr(wpt), L.ptr(wpj), L.i32(_planes(wpj)), L.ptr(wpt3), L.i32(_planes(wpt3)),
-                                            L.f32(2.0 * float(coeff) / max(n, 1)), L.ptr(act), L.ptr(dz), L.ptr(tb), L.ptr(eb), L.i64(n),
-                                            L.ptr(dw0), L.ptr(db0), L.ptr(dwh), L.ptr(dbh), L.ptr(dw4), L.ptr(db4), L.ptr(dw7), L.i32(max_cus), L.stream()),
-                    'sdf_mlp_eik_bwd')
+            L.call('sdf_mlp_eik_bwd', xc, u, wp, wpt, wpj, _planes(wpj), wpt3, _planes(wpt3), 2.0 * float(coeff) / max(n, 1), act, dz, tb, eb, n, dw0,
+                   db0, dwh, dbh, dw4, db4, dw7, max_cus)
             ctx.arena = arena
         return ret
 

@@ -70,8 +70,7 @@ class _PoseFn(torch.autograd.Function):
         A = torch.empty(B, J, 4, 4, dtype=torch.float32, device=fp.device)
         G = torch.empty(B, J, 12, dtype=torch.float32, device=fp.device)
         jbs = 0 if jc.shape[0] == 1 else J * 3
-        L.check(L.lib().d3h_smplx_pose_fwd(L.ptr(fpc), L.ptr(jc), L.i32(jbs), L.ptr(parents32), L.i32(J), L.i32(B), L.ptr(A), L.ptr(G), L.stream()),
-                'smplx_pose_fwd')
+        L.call('smplx_pose_fwd', fpc, jc, jbs, parents32, J, B, A, G)
         ctx.save_for_backward(fpc, jc, parents32, G)
         ctx.jshape = joints.shape
         return A
@@ -84,8 +83,7 @@ class _PoseFn(torch.autograd.Function):
         d_fp = torch.empty_like(fpc)
         d_J = torch.empty(B, J, 3, dtype=torch.float32, device=fpc.device) if ctx.needs_input_grad[1] else None
         jbs = 0 if jc.shape[0] == 1 else J * 3
-        L.check(L.lib().d3h_smplx_pose_bwd(L.ptr(fpc), L.ptr(jc), L.i32(jbs), L.ptr(parents32), L.i32(J), L.i32(B), L.ptr(G), L.ptr(dA.contiguous().float()),
-                                           L.ptr(d_fp), L.ptr(d_J), L.stream()), 'smplx_pose_bwd')
+        L.call('smplx_pose_bwd', fpc, jc, jbs, parents32, J, B, G, dA.contiguous().float(), d_fp, d_J)
         if d_J is not None and tuple(d_J.shape) != tuple(ctx.jshape):
             d_J = d_J.sum_to_size(ctx.jshape)
         return d_fp, d_J, None

@@ -18,10 +18,6 @@ MAX_MAPS = 3
 MAX_CHANNELS = 4
 
 
-def _ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else L.ptr(t).value for t in tensors])
-
-
 def _hwc(maps):
     flat = [int(v) for m in maps for v in m.shape[1:4]]
     return (ctypes.c_int * len(flat))(*flat)
@@ -34,8 +30,7 @@ class _LookupFn(torch.autograd.Function):
         npix, F = B * H * W, tri.shape[0]
         new = torch.zeros if F == 0 else torch.empty                       # F == 0 launches nothing
         outs = [new(B, H, W, m.shape[-1], dtype=torch.float32, device=rast.device) for m in maps]
-        L.check(L.lib().d3h_texmat_fwd(L.ptr(rast), L.ptr(v_tex), L.i64(v_tex.shape[0]), L.ptr(tri), L.i64(F), L.i64(npix), L.i32(len(maps)),
-                                       _ptrs(maps), _hwc(maps), L.i32(bnd), _ptrs(outs), L.stream()), 'texmat_fwd')
+        L.call('texmat_fwd', rast, v_tex, v_tex.shape[0], tri, F, npix, len(maps), L.ptr_array(maps), _hwc(maps), bnd, L.ptr_array(outs))
         ctx.save_for_backward(rast, v_tex, tri, *maps)
         ctx.bnd = bnd
         return tuple(outs)
@@ -48,9 +43,8 @@ class _LookupFn(torch.autograd.Function):
         grads = [L.zeros_like(m) if n and g is not None else None for m, n, g in zip(maps, need, g_outs)]
         g_in = [None if d is None else g.contiguous().float() for d, g in zip(grads, g_outs)]
         if any(d is not None for d in grads):
-            L.check(L.lib().d3h_texmat_bwd(L.ptr(rast), L.ptr(v_tex), L.i64(v_tex.shape[0]), L.ptr(tri), L.i64(tri.shape[0]), L.i64(B * H * W),
-                                           L.i32(len(maps)), _ptrs(maps), _hwc(maps), L.i32(ctx.bnd), _ptrs(g_in), _ptrs(grads), L.stream()),
-                    'texmat_bwd')
+            L.call('texmat_bwd', rast, v_tex, v_tex.shape[0], tri, tri.shape[0], B * H * W, len(maps), L.ptr_array(maps), _hwc(maps), ctx.bnd, L.ptr_array(g_in),
+                   L.ptr_array(grads))
         return (None, None, None, None) + tuple(grads)
 
 

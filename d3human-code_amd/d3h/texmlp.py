@@ -17,7 +17,7 @@ ENC_DIMS = N_LEVELS * N_FEATURES
 
 
 def grid_param_count(per_level_scale=PER_LEVEL_SCALE, base_res=BASE_RES):
-    return int(L.lib().d3h_hashgrid_param_floats(ctypes.c_double(per_level_scale), L.i32(base_res)))
+    return L.query('hashgrid_param_floats', per_level_scale, base_res)
 
 
 def _f6(v):
@@ -75,8 +75,7 @@ class _TexMLPFn(torch.autograd.Function):
         tab = table.contiguous().float()
         m = mask.reshape(-1).contiguous().float() if mask is not None else None
         out = torch.empty(n, 6, dtype=torch.float32, device=x.device)
-        L.check(L.lib().d3h_texmlp_fwd(L.ptr(xs), L.ptr(m), L.ptr(tab), L.ptr(wcat), L.i64(n), ctypes.c_double(PER_LEVEL_SCALE), L.i32(BASE_RES),
-                                       _f6(bbox), _f6(omin), _f6(omax), L.ptr(out), None, L.stream()), 'texmlp_fwd')
+        L.call('texmlp_fwd', xs, m, tab, wcat, n, PER_LEVEL_SCALE, BASE_RES, _f6(bbox), _f6(omin), _f6(omax), out, None)
         ctx.save_for_backward(xs, m if m is not None else xs.new_empty(0), tab, wcat)
         ctx.table_leaf = weakref.ref(table) if table.is_leaf else None
         ctx.w_leaves = (w1, w2, w3) if all(w.is_leaf and w.dtype == torch.float32 and w.is_contiguous() for w in (w1, w2, w3)) else None
@@ -88,7 +87,6 @@ class _TexMLPFn(torch.autograd.Function):
         xs, m, tab, wcat = ctx.saved_tensors
         bbox, omin, omax, gs, has_mask, xshape, s1, s2, s3 = ctx.meta
         n = xs.shape[0]
-        lib = L.lib()
         need_tab, need_w, need_x = ctx.needs_input_grad[2], any(ctx.needs_input_grad[3:6]), ctx.needs_input_grad[0]
         # Frame-parallel step: leaf gradients are produced inside the step's all-reduce arena (d3h.gradarena).  The first contribution of a
         # pass takes the parameter's (pre-zeroed) slice and returns it; a later one accumulates onto the slice with the same atomics and
@@ -116,12 +114,11 @@ class _TexMLPFn(torch.autograd.Function):
         genc = torch.empty(n, 10, dtype=torch.float32, device=xs.device)       # d(encoding) between the two halves of the split backward
         gc = g.reshape(-1, 6).contiguous().float()
         mp = m if has_mask else None
-        args = lambda: (L.ptr(xs), L.ptr(mp), L.ptr(tab), L.ptr(wcat), L.i64(n), ctypes.c_double(PER_LEVEL_SCALE), L.i32(BASE_RES), _f6(bbox),
-                        _f6(omin), _f6(omax), L.f32(gs))
+        args = (xs, mp, tab, wcat, n, PER_LEVEL_SCALE, BASE_RES, _f6(bbox), _f6(omin), _f6(omax), gs)
         side = _scatter_stream(xs) if (ASYNC_TABLE_GRAD and need_tab and need_x and first_contribution) else None
         if side is None:
             _join_scatter()            # an earlier node's table gradient may still be in flight: the engine is about to add ours to it
-            L.check(lib.d3h_texmlp_bwd(*args(), L.i32(0), L.ptr(gc), L.ptr(d_tab), L.ptr(d_w), L.ptr(d_x), L.ptr(genc), L.stream()), 'texmlp_bwd')
+            L.call('texmlp_bwd', *args, 0, gc, d_tab, d_w, d_x, genc)
         else:
             # The table gradient is a leaf result and its scatter is bound by fabric atomics (0.6 ms at 4 x 1024^2), while the position
             # gradient is on the critical path of the backward.  MLP half and position gradient on this stream; the scatter on a second
@@ -131,13 +128,13 @@ class _TexMLPFn(torch.autograd.Function):
             _join_scatter()
             if DX_FUSED:
                 # (the MLP half writes d_x itself: csrc/texmlp.hip, texmlp_bwd_mlp_h2_kernel)
-                L.check(lib.d3h_texmlp_bwd(*args(), L.i32(0), L.ptr(gc), None, L.ptr(d_w), L.ptr(d_x), L.ptr(genc), L.stream()), 'texmlp_bwd_mlp_dx')
+                L.call('texmlp_bwd', *args, 0, gc, None, d_w, d_x, genc)
             else:
-                L.check(lib.d3h_texmlp_bwd(*args(), L.i32(0), L.ptr(gc), None, L.ptr(d_w), None, L.ptr(genc), L.stream()), 'texmlp_bwd_mlp')
-                L.check(lib.d3h_texmlp_bwd(*args(), L.i32(1), L.ptr(genc), None, None, L.ptr(d_x), None, L.stream()), 'texmlp_bwd_dx')
+                L.call('texmlp_bwd', *args, 0, gc, None, d_w, None, genc)
+                L.call('texmlp_bwd', *args, 1, genc, None, None, d_x, None)
             side.wait_stream(main)
             with L.use_stream(side):
-                L.check(lib.d3h_texmlp_bwd(*args(), L.i32(1), L.ptr(genc), L.ptr(d_tab), None, None, None, L.stream()), 'texmlp_bwd_table')
+                L.call('texmlp_bwd', *args, 1, genc, d_tab, None, None, None)
             for t in (xs, tab, genc, d_tab) + ((mp,) if mp is not None else ()):
                 t.record_stream(side)
             _PENDING.append(side)
@@ -165,8 +162,7 @@ class _GridEncodeFn(torch.autograd.Function):
         tab = table.contiguous().float()
         enc = torch.empty(n, ENC_DIMS, dtype=torch.float32, device=x.device)
         unit = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0)
-        L.check(L.lib().d3h_texmlp_fwd(L.ptr(xs), None, L.ptr(tab), None, L.i64(n), ctypes.c_double(PER_LEVEL_SCALE), L.i32(BASE_RES), _f6(unit),
-                                       None, None, None, L.ptr(enc), L.stream()), 'hashgrid_fwd')
+        L.call('texmlp_fwd', xs, None, tab, None, n, PER_LEVEL_SCALE, BASE_RES, _f6(unit), None, None, None, enc)
         ctx.save_for_backward(xs, tab)
         ctx.xshape = x.shape
         return enc
@@ -180,9 +176,8 @@ class _GridEncodeFn(torch.autograd.Function):
         d_tab = L.zeros_like(tab) if ctx.needs_input_grad[1] else None
         d_x = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
         unit = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0)
-        L.check(L.lib().d3h_texmlp_bwd(L.ptr(xs), None, L.ptr(tab), None, L.i64(xs.shape[0]), ctypes.c_double(PER_LEVEL_SCALE), L.i32(BASE_RES),
-                                       _f6(unit), None, None, L.f32(1.0), L.i32(1), L.ptr(g.contiguous().float()), L.ptr(d_tab), None, L.ptr(d_x),
-                                       None, L.stream()), 'hashgrid_bwd')
+        L.call('texmlp_bwd', xs, None, tab, None, xs.shape[0], PER_LEVEL_SCALE, BASE_RES, _f6(unit), None, None, 1.0, 1, g.contiguous().float(),
+               d_tab, None, d_x, None)
         return (d_x.reshape(ctx.xshape) if d_x is not None else None), d_tab
 
 

@@ -66,7 +66,7 @@ class _MipBuildFn(torch.autograd.Function):
         bt, C, F = tex.shape[0], tex.shape[-1], 6 if cube else 1
         pyr = torch.empty(sum(bt * F * h * w * C for h, w in sizes), dtype=torch.float32, device=tex.device)
         pyr[:tex.numel()].copy_(tex.reshape(-1))
-        L.check(L.lib().d3h_texmip_build(L.ptr(pyr), L.i32(bt), L.i32(F), L.i32(C), L.i32(len(sizes)), _hw(sizes), L.stream()), 'texmip_build')
+        L.call('texmip_build', pyr, bt, F, C, len(sizes), _hw(sizes))
         ctx.meta = (tuple(tex.shape), sizes, F)
         return pyr
 
@@ -74,8 +74,7 @@ class _MipBuildFn(torch.autograd.Function):
     def backward(ctx, g_pyr):
         shape, sizes, F = ctx.meta
         g_tex = torch.empty(shape, dtype=torch.float32, device=g_pyr.device)
-        L.check(L.lib().d3h_texmip_bwd(L.ptr(g_pyr.contiguous()), L.ptr(g_tex), L.i32(shape[0]), L.i32(F), L.i32(shape[-1]), L.i32(len(sizes)),
-                                       _hw(sizes), L.stream()), 'texmip_bwd')
+        L.call('texmip_bwd', g_pyr.contiguous(), g_tex, shape[0], F, shape[-1], len(sizes), _hw(sizes))
         return g_tex, None, None
 
 
@@ -85,8 +84,7 @@ class _LookupFn(torch.autograd.Function):
         bt, C, sizes, filt, bnd = meta
         nb, h, w = uv.shape[:3]
         out = torch.empty(nb, h, w, C, dtype=torch.float32, device=uv.device)
-        L.check(L.lib().d3h_texlookup_fwd(L.ptr(pyr), L.i32(bt), L.i32(C), L.i32(len(sizes)), _hw(sizes), L.ptr(uv), L.ptr(uv_da), L.ptr(bias),
-                                          L.i32(nb), L.i32(h), L.i32(w), L.i32(filt), L.i32(bnd), L.ptr(out), L.stream()), 'texlookup_fwd')
+        L.call('texlookup_fwd', pyr, bt, C, len(sizes), _hw(sizes), uv, uv_da, bias, nb, h, w, filt, bnd, out)
         ctx.save_for_backward(pyr, uv, uv_da, bias)
         ctx.meta = meta
         return out
@@ -102,9 +100,8 @@ class _LookupFn(torch.autograd.Function):
         d_da = torch.empty_like(uv_da) if need[2] else None
         d_bias = torch.empty_like(bias) if need[3] else None
         if d_pyr is not None or d_uv is not None or d_da is not None or d_bias is not None:
-            L.check(L.lib().d3h_texlookup_bwd(L.ptr(pyr), L.i32(bt), L.i32(C), L.i32(len(sizes)), _hw(sizes), L.ptr(uv), L.ptr(uv_da), L.ptr(bias),
-                                              L.i32(nb), L.i32(h), L.i32(w), L.i32(filt), L.i32(bnd), L.ptr(g_out.contiguous()), L.ptr(d_pyr),
-                                              L.ptr(d_uv), L.ptr(d_da), L.ptr(d_bias), L.stream()), 'texlookup_bwd')
+            L.call('texlookup_bwd', pyr, bt, C, len(sizes), _hw(sizes), uv, uv_da, bias, nb, h, w, filt, bnd, g_out.contiguous(), d_pyr, d_uv, d_da,
+                   d_bias)
         return d_pyr, d_uv, d_da, d_bias, None
 
 

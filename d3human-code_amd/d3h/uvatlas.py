@@ -69,8 +69,7 @@ def make_atlas(v_pos, t_pos_idx, resolution):
     uvs = torch.empty(3 * F, 2, dtype=torch.float32, device=dev)
     t_tex_idx = torch.empty(F, 3, dtype=torch.int64, device=dev)
     rot = torch.empty(F, dtype=torch.uint8, device=dev)
-    L.check(L.lib().d3h_uvatlas_layout(L.ptr(v), L.i64(v.shape[0]), L.ptr(t), L.i32(t.dtype == torch.int64), L.i64(F), L.i32(s), L.i32(nx), L.i32(H), L.i32(W),
-                                       L.ptr(uvs), L.ptr(t_tex_idx), L.ptr(rot), L.stream()), 'uvatlas_layout')
+    L.call('uvatlas_layout', v, v.shape[0], t, t.dtype == torch.int64, F, s, nx, H, W, uvs, t_tex_idx, rot)
     return Atlas(uvs, t_tex_idx, t_pos_idx.reshape(-1), rot, s, nx, ny, (H, W))
 
 
@@ -84,9 +83,8 @@ def bake_positions(atlas, v_pos, t_pos_idx):
     pos = torch.empty(1, H, W, 3, dtype=torch.float32, device=dev)
     owned, inside = (torch.empty(1, H, W, 1, dtype=torch.float32, device=dev) for _ in range(2))
     tri = torch.empty(1, H, W, dtype=torch.int32, device=dev)
-    L.check(L.lib().d3h_uvatlas_bake(L.ptr(v), L.i64(v.shape[0]), L.ptr(t), L.i32(t.dtype == torch.int64), L.i64(F), L.ptr(atlas.rot.contiguous()),
-                                     L.i32(atlas.s), L.i32(atlas.nx), L.i32(atlas.ny), L.i32(H), L.i32(W), L.ptr(pos), L.ptr(owned), L.ptr(inside), L.ptr(tri),
-                                     L.stream()), 'uvatlas_bake')
+    L.call('uvatlas_bake', v, v.shape[0], t, t.dtype == torch.int64, F, atlas.rot.contiguous(), atlas.s, atlas.nx, atlas.ny, H, W, pos, owned, inside,
+           tri)
     return pos, owned, inside, tri
 
 
@@ -103,7 +101,7 @@ def mip2x2_fwd(x):
         raise ValueError(f"mip2x2: H and W must be even and at least 2, got {(H, W)} (the reference's gradient has the wrong shape there)")
     x = x.detach().float().contiguous()
     y = torch.empty(N, H // 2, W // 2, C, dtype=torch.float32, device=x.device)
-    L.check(L.lib().d3h_mip2x2_fwd(L.ptr(x), L.i64(N), L.i32(H // 2), L.i32(W // 2), L.i32(C), L.ptr(y), L.stream()), 'mip2x2_fwd')
+    L.call('mip2x2_fwd', x, N, H // 2, W // 2, C, y)
     return y
 
 
@@ -114,7 +112,7 @@ def mip2x2_bwd(dy):
     N, h, w, C = dy.shape
     dy = dy.detach().float().contiguous()
     dx = torch.empty(N, 2 * h, 2 * w, C, dtype=torch.float32, device=dy.device)
-    L.check(L.lib().d3h_mip2x2_bwd(L.ptr(dy), L.i64(N), L.i32(h), L.i32(w), L.i32(C), L.ptr(dx), L.stream()), 'mip2x2_bwd')
+    L.call('mip2x2_bwd', dy, N, h, w, C, dx)
     return dx
 
 

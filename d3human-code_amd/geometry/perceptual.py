@@ -23,7 +23,7 @@ class _BiasReLU6Fn(torch.autograd.Function):
         N, C = x.shape[0], x.shape[1]
         HW = x.numel() // max(N * C, 1)
         y = torch.empty_like(x)
-        L.check(L.lib().d3h_bias_relu6_fwd(L.ptr(x), L.ptr(b.contiguous()), L.i64(N), L.i32(C), L.i64(HW), L.ptr(y), L.stream()), 'bias_relu6_fwd')
+        L.call('bias_relu6_fwd', x, b.contiguous(), N, C, HW, y)
         ctx.save_for_backward(y)
         return y
 
@@ -33,7 +33,7 @@ class _BiasReLU6Fn(torch.autograd.Function):
         y, = ctx.saved_tensors
         g = g.contiguous()
         gx = torch.empty_like(g)
-        L.check(L.lib().d3h_relu6_bwd(L.ptr(y), L.ptr(g), L.i64(y.numel()), L.ptr(gx), L.stream()), 'relu6_bwd')
+        L.call('relu6_bwd', y, g, y.numel(), gx)
         return gx, None
 
 

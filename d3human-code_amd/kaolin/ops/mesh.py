@@ -37,16 +37,15 @@ def sample_points(vertices, faces, num_samples, areas=None, face_features=None, 
             pts = torch.empty(num_samples, 3, dtype=torch.float32, device=v.device)
             pick = torch.empty(num_samples, dtype=torch.int64, device=v.device)
             cdf = torch.empty(nf, dtype=torch.float32, device=v.device)
-            L.check(L.lib().d3h_sample_surface(L.ptr(vc), L.ptr(fc), L.i32(nf), L.ptr(rnd), L.i32(num_samples), L.ptr(cdf), L.ptr(pts), L.ptr(pick),
-                                               L.stream()), 'sample_surface')
+            L.call('sample_surface', vc, fc, nf, rnd, num_samples, cdf, pts, pick)
             return pts[None], pick[None]
         if areas is None:
             areas = torch.empty(nf, dtype=torch.float32, device=v.device)
-            L.check(L.lib().d3h_face_areas(L.ptr(vc), L.ptr(fc), L.i32(nf), L.ptr(areas), L.stream()), 'face_areas')
+            L.call('face_areas', vc, fc, nf, areas)
         pick = torch.multinomial(_pick_weights(areas), num_samples, replacement=True)
         uw = torch.rand(num_samples, 2, device=v.device)
         pts = torch.empty(num_samples, 3, dtype=torch.float32, device=v.device)
-        L.check(L.lib().d3h_sample_faces(L.ptr(vc), L.ptr(fc), L.ptr(pick), L.ptr(uw), L.i32(num_samples), L.ptr(pts), L.stream()), 'sample_faces')
+        L.call('sample_faces', vc, fc, pick, uw, num_samples, pts)
         return pts[None], pick[None]
     a, b, c = v[faces[:, 0]], v[faces[:, 1]], v[faces[:, 2]]
     if areas is None:

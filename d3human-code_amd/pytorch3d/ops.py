@@ -90,7 +90,7 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, re
         dist = torch.empty(B, P, dtype=torch.float32, device=p1.device)
         for b in range(B):
             a, t = p1[b].detach().contiguous().float(), p2[b].detach().contiguous().float()
-            L.check(L.lib().d3h_knn1(L.ptr(a), L.i32(P), L.ptr(t), L.i32(t.shape[0]), L.ptr(idx[b]), L.ptr(dist[b]), L.stream()), 'knn1')
+            L.call('knn1', a, P, t, t.shape[0], idx[b], dist[b])
         nn = None
         if return_nn:
             nn = torch.gather(p2, 1, idx.long()[..., None].expand(-1, -1, p2.shape[-1]))[:, :, None]

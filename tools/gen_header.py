@@ -1,5 +1,6 @@
 """Regenerate include/d3h.h from the extern "C" definitions in d3human-code_amd/csrc/*.hip (signatures + their leading comments),
-grouped per source file with the reference interface each group replaces."""
+grouped per source file with the reference interface each group replaces, and d3human-code_amd/d3h/_abi.py, the same signatures as
+a table the ctypes binding (d3h/_lib.py) sets argtypes from and checks every call against."""
 import glob, os, re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GROUPS = {
@@ -60,6 +61,7 @@ head = head + f'''
 #define D3H_ABI_VERSION {ver}
 '''
 out = [head]
+sigs = []                      # every declaration, in header order: the rows of d3h/_abi.py
 for fn in ORDER:
     s = open(os.path.join(ROOT, 'd3human-code_amd', 'csrc', fn)).read()
     out.append(f'\n/* ==== {fn}: replaces {GROUPS[fn]} ==== */\n')
@@ -67,6 +69,7 @@ for fn in ORDER:
         comment = ''.join('/* ' + l.strip()[2:].strip() + ' */\n' for l in m.group(1).splitlines() if l.strip() and not l.strip().startswith('// ---'))
         sig = ' '.join(m.group(2).split())
         out.append(comment + sig + ';\n')
+        sigs.append(sig)
 # compile-time variants: the same sources built a second time under other entry-point names (see csrc/deform_mlp*.hip)
 VARIANTS = [('deform_mlp.hip', 'sdf_mlp.hip', 'offset network MLP_deform: geometry/mlp.py:77-118 (seq stage, geometry/hmsdf.py:658-665); sdf_mlp.hip compiled '
              'with a 51-wide encoding and a 3-output head, the 136-float pose code folded into the first bias by the caller'),
@@ -82,6 +85,27 @@ for wrapper, base, what in VARIANTS:
         name = re.search(r'\b(d3h_\w+)\s*\(', sig).group(1)
         if name in ren:
             out.append(sig.replace(name, ren[name]) + ';\n')
+            sigs.append(sig.replace(name, ren[name]))
 out.append('\n#ifdef __cplusplus\n}\n#endif\n#endif\n')
 open(os.path.join(ROOT, 'include', 'd3h.h'), 'w').write(''.join(out))
 print('wrote include/d3h.h')
+
+# ---- d3h/_abi.py: {name: (return type, ((C type, parameter name), ...))}.  A name declared twice (timing.hip: the emulation's stubs
+# carry no parameter names) is one row, the declaration with names
+abi = {}
+for sig in sigs:
+    ret, name, params = re.fullmatch(r'(.+?)\s*\b(d3h_\w+)\s*\((.*)\)', sig).groups()
+    row = []
+    for p in ([] if params.strip() in ('', 'void') else params.split(',')):
+        m = re.fullmatch(r'\s*(.*?[\s*])(\w+)\s*', p)
+        ctype, pname = (m.group(1), m.group(2)) if m and m.group(2) not in ('int', 'long', 'int64_t', 'float', 'double', 'unsigned') else (p, '')
+        row.append((' '.join(ctype.split()), pname))
+    if name not in abi or all(n for _, n in row):
+        abi[name] = (ret, tuple(row))
+lines = ['"""Signatures of the C ABI (include/d3h.h) as data: {entry point: (return type, ((C type, parameter name), ...))}.\n'
+         'GENERATED by tools/gen_header.py from the extern "C" definitions in d3human-code_amd/csrc/ -- do not edit by hand."""\n', 'ABI = {\n']
+for name, (ret, row) in abi.items():
+    lines.append(f'    {name!r}: ({ret!r}, ({"".join(repr(r) + ", " for r in row)})),\n')
+lines.append('}\n')
+open(os.path.join(ROOT, 'd3human-code_amd', 'd3h', '_abi.py'), 'w').write(''.join(lines))
+print('wrote d3human-code_amd/d3h/_abi.py')
