@@ -601,7 +601,10 @@ __global__ __launch_bounds__(256) void seq_losses_bwd_kernel(SeqLossCfg k, const
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const float m = mw[q] * alpha;
-            float dm = g[q] * 2.0f * (m - gt[q].w);
+            const float dm = g[q] * 2.0f * (m - gt[q].w);
+            // d(image loss) / d(mask) is summed on its own and only then added to the mask term: colour products of opposite sign (an HDR colour
+            // above its target in one channel, below in another) cancel among themselves, and a mask term added first was rounded at their size
+            float dc = 0.f;
             const float tc[3] = {gt[q].x, gt[q].y, gt[q].z};
             const float go = g[3 + q] / 3.0f;
 #pragma unroll
@@ -615,9 +618,9 @@ __global__ __launch_bounds__(256) void seq_losses_bwd_kernel(SeqLossCfg k, const
                 loss_elem_bwd(k.loss, a, t, go, ga, gtt);
                 if (k.tonemap) ga = (a0 > 0.f && a0 < 65535.f) ? bwd_srgb(la, ga) / (a0 + 1.0f) : 0.f;      // as image_loss_bwd_kernel (loss.cu:44-62)
                 d_rgb[c] += ga * m;
-                dm += ga * rgb;
+                dc += ga * rgb;
             }
-            d_alpha += dm * mw[q];
+            d_alpha += (dm + dc) * mw[q];
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) dp[k.cs + c] = d_rgb[c];

@@ -68,16 +68,29 @@ def image_loss(img, target, loss='l1', tonemapper='none'):
     return l.mean()
 
 
-def ssim(a, b):
-    g = torch.tensor([math.exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)])
-    g = (g / g.sum())[:, None]
+def ssim_window2d(C, dtype, device, window=None):
+    """the [C,1,11,11] depthwise filter: ssim_loss.py:22-31 (float32 Gaussian, normalised in float32), or the outer product of a given
+    1-D `window` of 11 weights formed in `dtype` (tests/loss64_cases.py hands the kernel's own weights to both of its references)"""
+    if window is None:
+        g = torch.tensor([math.exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)])
+        g = (g / g.sum())[:, None]
+    else:
+        g = torch.as_tensor(window).to(dtype)[:, None]
+    return (g @ g.t()).to(dtype)[None, None].expand(C, 1, 11, 11).contiguous().to(device)
+
+
+def ssim_map(a, b, window=None, C1=0.01 ** 2, C2=0.03 ** 2):
+    """ssim_loss.py:33-63 before the mean: the SSIM value of every pixel"""
     C = a.shape[-3]
-    win = (g @ g.t()).to(a.dtype)[None, None].expand(C, 1, 11, 11).contiguous().to(a.device)
+    win = ssim_window2d(C, a.dtype, a.device, window)
     conv = lambda x: F.conv2d(x, win, padding=5, groups=C)
     mu1, mu2 = conv(a), conv(b)
     s11, s22, s12 = conv(a * a) - mu1 * mu1, conv(b * b) - mu2 * mu2, conv(a * b) - mu1 * mu2
-    C1, C2 = 0.01 ** 2, 0.03 ** 2
-    return (((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s11 + s22 + C2))).mean()
+    return ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s11 + s22 + C2))
+
+
+def ssim(a, b, window=None, C1=0.01 ** 2, C2=0.03 ** 2):
+    return ssim_map(a, b, window, C1, C2).mean()
 
 
 def sdf_reg_loss(sdf, edges):
