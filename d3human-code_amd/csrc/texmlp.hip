@@ -63,7 +63,7 @@ __device__ __forceinline__ void encode(const GridCfg& g, const float* __restrict
                 idx += (pg[d] + bit) * stride;
                 stride *= res;
             }
-            if (idx >= g.size[l]) idx -= g.size[l];     // only x == 1 on level 0 (scale 15 -> corner 16) can wrap
+            if (idx >= g.size[l]) idx -= g.size[l];     // a corner index reaches res on levels 0, 2 and 3 (scale + 0.5 crosses an integer below x == 1): it spills into the next row, or wraps
             float2 v = tab[idx];
             f0 = fmaf(w, v.x, f0);
             f1 = fmaf(w, v.y, f1);
@@ -104,7 +104,7 @@ __device__ __forceinline__ void encode_dx(const GridCfg& g, const float* __restr
                 idx += (pg[d] + bit) * stride;
                 stride *= res;
             }
-            if (idx >= g.size[l]) idx -= g.size[l];     // only x == 1 on level 0 (scale 15 -> corner 16) can wrap
+            if (idx >= g.size[l]) idx -= g.size[l];     // a corner index reaches res on levels 0, 2 and 3 (scale + 0.5 crosses an integer below x == 1): it spills into the next row, or wraps
             float2 v = tab[g.offset[l] + idx];
             f0 = fmaf(w, v.x, f0);
             f1 = fmaf(w, v.y, f1);
@@ -1097,6 +1097,15 @@ GridCfg make_cfg(double per_level_scale, int base_res) {
     return g;
 }
 
+// D3H_TEX_GRID_CAP=<k> (read per call): at most k workgroups for every kernel of this file, so that the persistent loops can be walked at a
+// small n (tests on the host emulation); unset or < 1: the caps below
+int grid_cap(int64_t want, int cap) {
+    const char* e = getenv("D3H_TEX_GRID_CAP");
+    const int k = e ? atoi(e) : 0;
+    if (k >= 1 && k < cap) cap = k;
+    return (int)(want < cap ? want : cap);
+}
+
 TexParams make_tp(const float* bbox, const float* omin, const float* omax, float in_grad_scale) {
     TexParams tp;
     for (int d = 0; d < 3; ++d) { tp.b0[d] = bbox[d]; tp.b1[d] = bbox[3 + d]; }
@@ -1132,9 +1141,9 @@ extern "C" int d3h_texmlp_fwd(const float* x, const float* mask, const float* ta
     // a quarter of them all eight of their tiles covered and the rest none (162 us per 4 x 1024^2 call); with one tile each the dispatcher
     // balances, background tiles retire at once
     const int64_t ntile = (n + 255) / 256;
-    const unsigned grid = (unsigned)(ntile < (1 << 20) ? ntile : (1 << 20));
+    const unsigned grid = (unsigned)grid_cap(ntile, 1 << 20);
     if (out && w && !enc_out)      // persistent waves keep the weights: 2039 (prime) workgroups, so that the covered tiles spread over all of them
-        hipLaunchKernelGGL(texmlp_fwd_mfma_kernel, dim3(grid < 2039u ? grid : 2039u), dim3(256), 0, (hipStream_t)stream, g, tp, x, mask, table, w, n, out);
+        hipLaunchKernelGGL(texmlp_fwd_mfma_kernel, dim3((unsigned)grid_cap(ntile, 2039)), dim3(256), 0, (hipStream_t)stream, g, tp, x, mask, table, w, n, out);
     else
         hipLaunchKernelGGL(texmlp_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, tp, x, mask, table, w, n, out, enc_out);
     d3h_ktime_end(kt, (hipStream_t)stream);
@@ -1153,7 +1162,7 @@ extern "C" int d3h_texmlp_bwd(const float* x, const float* mask, const float* ta
     int64_t ntile = (n + 255) / 256;
     // 1021 (prime) workgroups: an image row is W/256 tiles, so with a power-of-two grid every workgroup would keep visiting the same
     // image columns and the ones over the (centred) body would get all the covered tiles
-    int grid = (int)(ntile < 1021 ? ntile : 1021);
+    int grid = grid_cap(ntile, 1021);
     hipStream_t s = (hipStream_t)stream;
     float* nof = nullptr;
     if (enc_only) {
@@ -1162,9 +1171,9 @@ extern "C" int d3h_texmlp_bwd(const float* x, const float* mask, const float* ta
         d3h_ktime_end(kt, s);
     } else if (genc_scratch) {
         // split backward: genc_scratch [n][10] carries d(encoding) (already scaled by in_grad_scale) between the two halves
-        int grid2 = (int)(ntile < 4093 ? ntile : 4093);
+        int grid2 = grid_cap(ntile, 4093);
         // MLP half: wave-granular (64-pixel) tiles, 509 (prime) workgroups of 4 waves -- two per CU, one flush of the weight gradients each
-        int gridm = (int)(ntile < 509 ? ntile : 509);
+        int gridm = grid_cap(ntile, 509);
         const int ktm = d3h_ktime_begin(D3H_KT_TEX_BWD_MLP, n, s);
         static int tex_h2 = -1;          // D3H_TEX_H2=0: the round-5 kernel (VALU mat-vecs + exact-f32 outer products), A/B
         if (tex_h2 < 0) { const char* e = getenv("D3H_TEX_H2"); tex_h2 = (e && e[0] == '0') ? 0 : 1; }
@@ -1173,8 +1182,8 @@ extern "C" int d3h_texmlp_bwd(const float* x, const float* mask, const float* ta
         // d_x from the MLP half (the h2 kernel only).  D3H_TEX_DX_FUSED=0 (read per call): the encoding half gathers the table again for it, A/B
         const char* ef = getenv("D3H_TEX_DX_FUSED");
         float* d_x_mlp = (tex_h2 && !(ef && ef[0] == '0')) ? d_x : nullptr;
-        if (tex_h2 && d_x_mlp) hipLaunchKernelGGL((texmlp_bwd_mlp_h2_kernel<true>), dim3((unsigned)(nwt8 < 251 ? nwt8 : 251)), dim3(512), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch, d_x_mlp);
-        else if (tex_h2) hipLaunchKernelGGL((texmlp_bwd_mlp_h2_kernel<false>), dim3((unsigned)(nwt8 < 251 ? nwt8 : 251)), dim3(512), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch, nof);
+        if (tex_h2 && d_x_mlp) hipLaunchKernelGGL((texmlp_bwd_mlp_h2_kernel<true>), dim3((unsigned)grid_cap(nwt8, 251)), dim3(512), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch, d_x_mlp);
+        else if (tex_h2) hipLaunchKernelGGL((texmlp_bwd_mlp_h2_kernel<false>), dim3((unsigned)grid_cap(nwt8, 251)), dim3(512), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch, nof);
         else hipLaunchKernelGGL(texmlp_bwd_mlp_kernel, dim3(gridm), dim3(256), 0, s, g, tp, x, mask, table, w, n, g_out, d_w, genc_scratch);
         d3h_ktime_end(ktm, s);
         if (d_x_mlp) d_x = nullptr;

@@ -14,8 +14,14 @@ PER_LEVEL_SCALE = math.exp(math.log(4096 / 16) / 15)
 def grid_layout(per_level_scale=PER_LEVEL_SCALE, base=16, n_levels=5):
     import numpy as np
     out, off = [], 0
+    f = np.float32
     for l in range(n_levels):
-        scale = float(np.float32(np.exp2(np.float32(l) * np.log2(np.float32(per_level_scale)))) * np.float32(base) - np.float32(1))
+        # exp2f(l * log2f(s)) * base - 1 in float32 with every step correctly rounded (evaluated in double, rounded once), which is what the C
+        # library gives make_cfg in csrc/texmlp.hip.  numpy's own float32 exp2 is one ulp above it on level 3 (47.50293 instead of 47.502926):
+        # as much as the rounding of p = x * scale + 0.5 itself.  Nothing reads make_cfg's values back: the witness that the two agree is
+        # tests/tex64_cases.py, where a scale one ulp off puts the float32-only routes 7 and 8 at band ratios of 4 to 6 instead of 1
+        y = f(f(l) * f(math.log2(float(f(per_level_scale)))))
+        scale = float(f(f(f(2.0 ** float(y)) * f(base)) - f(1)))
         res = int(math.ceil(scale)) + 1
         size = (res ** 3 + 7) // 8 * 8
         out.append((scale, res, off, size))
