@@ -1,5 +1,5 @@
-// d3h_h2.h -- the two-plane fp16 operand split ("h2") for kernels outside the SDF-network sources (which carry their own copy inside their
-// per-network namespace, sdf_mlp_x3.h: the error argument and the measurements are there).
+// d3h_h2.h -- the two-plane fp16 operand split ("h2"): the packed-f16 conversions every h2 kernel uses, and the 32x32x16 fragments of the
+// kernels outside the SDF-network sources (sdf_mlp_x3.h has the 16x16x32 ones, the error argument and the measurements).
 //   a = a_h + 2^-11 a_m',  a_h = fp16(a),  a_m' = fp16(2^11 (a - a_h))                       22 significant bits
 //   a b ~ a_h b_h + 2^-11 (a_h b_m' + a_m' b_h)                                               three products, the cross terms in `lo`
 // Operand layout of v_mfma_f32_32x32x16_f16 (one dword = two fp16, low half first): lane = i + 32 h holds, in 4 dwords, k-steps 8 h .. 8 h + 7

@@ -910,9 +910,6 @@ __device__ __forceinline__ void sdf_mlp_bwd_dw_body(const float* __restrict__ dz
                 for (int r = 0; r < 16; ++r) {
                     int row = (rg * 2 + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                     atomicAdd(&dW[(size_t)row * ld + coloff + col], acc[a][b][r]);
-#ifdef D3H_DW_DOUBLEFLUSH      // timing experiment: the flush a second time with zeros (same results) -- the difference is what it costs
-                    atomicAdd(&dW[(size_t)row * ld + coloff + col], acc[a][b][r] * 0.f);
-#endif
                 }
             }
         }
@@ -981,7 +978,7 @@ constexpr int DWX_PITCH = 12;
 #define D3H_MFMA32_BF16X8(a, b, c) \
     __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(d3h_bf16x8, a), __builtin_bit_cast(d3h_bf16x8, b), c, 0, 0, 0)
 #define D3H_MFMA32_F16X8(a, b, c) \
-    __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(d3h_f16x8, a), __builtin_bit_cast(d3h_f16x8, b), c, 0, 0, 0)
+    __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(d3h_h2_f16x8, a), __builtin_bit_cast(d3h_h2_f16x8, b), c, 0, 0, 0)
 #else
 #define D3H_MFMA32_BF16X8(a, b, c) emul::mfma_32x32x16bf16(a, b, c)
 #define D3H_MFMA32_F16X8(a, b, c) emul::mfma_32x32x16f16(a, b, c)
@@ -1012,20 +1009,10 @@ __global__ __launch_bounds__(512) void sdf_mlp_bwd_dw_layers_x3_kernel(const flo
                                                                        const int* __restrict__ tile_count, const float* __restrict__ a2_base,
                                                                        const float* __restrict__ b2_base) {
     constexpr int NP = 3;
-#ifndef D3H_DWX_PIPE
-#define D3H_DWX_PIPE 0
-#endif
-    // D3H_DWX_PIPE = 1: TWO LDS images; the transposition of tile t + 1 is interleaved, instruction by instruction, with the MFMAs of tile t (one
-    // barrier per tile instead of two; sched_group_barrier: one MFMA, then four VALU and one LDS instruction of the put) -- 108 KB of LDS
-    constexpr int NIMG = D3H_DWX_PIPE ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) unsigned TA3s[NIMG][NP * 256 * DWX_PITCH];
-    __shared__ __attribute__((aligned(16))) unsigned TB3s[NIMG][NP * 128 * DWX_PITCH];
-    unsigned* TA3 = TA3s[0];
-    unsigned* TB3 = TB3s[0];
-#ifdef D3H_DWX_PROBE_LDSPAD      // (diagnostic: a larger LDS footprint, so that fewer / no other workgroups share the CU)
-    __shared__ volatile unsigned ldspad[D3H_DWX_PROBE_LDSPAD / 4];
-    ldspad[threadIdx.x * 16 % (D3H_DWX_PROBE_LDSPAD / 4)] = threadIdx.x;
-#endif
+    __shared__ __attribute__((aligned(16))) unsigned TA3s[NP * 256 * DWX_PITCH];
+    __shared__ __attribute__((aligned(16))) unsigned TB3s[NP * 128 * DWX_PITCH];
+    unsigned* TA3 = TA3s;
+    unsigned* TB3 = TB3s;
     // The kernel needs 180 VGPRs and claims all 256: see THE CO-RESIDENCY RULE in sdf_mlp_x3.h -- a foreign wave sharing a SIMD with a wave that issues
     // bf16 MFMAs gets wrong packed-f32 results (this kernel, on the eikonal side stream, was where it was first seen: lbs_bwd_kernel's 3x3 algebra
     // on the main stream).  The __syncthreads() that closes every tile below is part of the rule (no wave ends while a sibling still multiplies).
@@ -1073,78 +1060,11 @@ __global__ __launch_bounds__(512) void sdf_mlp_bwd_dw_layers_x3_kernel(const flo
     if (t >= ngroups) return;             // (block-uniform) nothing to add: skip the zero-valued atomic flush
     const u32x4 ones = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
     issue(t);
-#ifdef D3H_DWX_PROBE_NOWORK
-    t = ngroups;
-#endif
-#if D3H_DWX_PIPE && !defined(D3H_EMULATED)
-    {
-        int cur = 0;
-        dwx_put(TA3s[0], 256, 16 * wave + 4 * (lane >> 4), lane & 15, ra[0]);
-        dwx_put(TA3s[0], 256, 16 * (wave + 8) + 4 * (lane >> 4), lane & 15, ra[1]);
-        dwx_put(TB3s[0], 128, 16 * wave + 4 * (lane >> 4), lane & 15, rbv);
-        __syncthreads();
-        if (t + (int)gridDim.x < ngroups) issue(t + gridDim.x);
-        for (; t < ngroups; t += gridDim.x) {
-            const bool bias_now = want_db && db && (!dz2 || t >= n16);
-            const bool more = t + (int)gridDim.x < ngroups;
-            const unsigned* TAc = TA3s[cur];
-            const unsigned* TBc = TB3s[cur];
-            u32x4 A[2][3], B[2][3];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    A[a][pl] = *(const u32x4*)(TAc + (pl * 256 + (rg * 2 + a) * 32 + i) * DWX_PITCH + 4 * h);
-                    B[a][pl] = *(const u32x4*)(TBc + (pl * 128 + (cg * 2 + a) * 32 + i) * DWX_PITCH + 4 * h);
-                }
-            // The next tile's transposition (its global loads were issued a whole tile ago) goes into the other image, interleaved with this
-            // tile's MFMAs: ONE basic block per variant (after the last tile the put writes an image nobody reads -- unconditional on purpose: a
-            // branch would split the block and the scheduler could not interleave), per MFMA five VALU instructions and one LDS write of the put
-            auto body = [&](auto with_bias) {
-                dwx_put(TA3s[cur ^ 1], 256, 16 * wave + 4 * (lane >> 4), lane & 15, ra[0]);
-                dwx_put(TA3s[cur ^ 1], 256, 16 * (wave + 8) + 4 * (lane >> 4), lane & 15, ra[1]);
-                dwx_put(TB3s[cur ^ 1], 128, 16 * wave + 4 * (lane >> 4), lane & 15, rbv);
-#pragma unroll
-                for (int a = 0; a < 2; ++a) {
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        f32x16 c = acc[a][b];
-                        c = D3H_MFMA32_BF16X8(A[a][2], B[b][0], c);
-                        c = D3H_MFMA32_BF16X8(A[a][0], B[b][2], c);
-                        c = D3H_MFMA32_BF16X8(A[a][1], B[b][1], c);
-                        c = D3H_MFMA32_BF16X8(A[a][1], B[b][0], c);
-                        c = D3H_MFMA32_BF16X8(A[a][0], B[b][1], c);
-                        c = D3H_MFMA32_BF16X8(A[a][0], B[b][0], c);
-                        acc[a][b] = c;
-                    }
-                    if (decltype(with_bias)::value) {
-                        accdb[a] = D3H_MFMA32_BF16X8(A[a][2], ones, accdb[a]);
-                        accdb[a] = D3H_MFMA32_BF16X8(A[a][1], ones, accdb[a]);
-                        accdb[a] = D3H_MFMA32_BF16X8(A[a][0], ones, accdb[a]);
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < (decltype(with_bias)::value ? 30 : 24); ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                }
-            };
-            (void)more;
-            if (bias_now) body(std::true_type{}); else body(std::false_type{});
-            __syncthreads();
-            if (t + 2 * (int)gridDim.x < ngroups) issue(t + 2 * gridDim.x);
-            cur ^= 1;
-        }
-    }
-#else
     for (; t < ngroups; t += gridDim.x) {
         // tile-packed element u = rb * 64 + lane: features 16 rb + 4 (lane >> 4) + 0..3 of point lane & 15
-#ifndef D3H_DWX_PROBE_NOPUT       // (diagnostic builds, results wrong: which part of the loop disturbs co-resident waves; see D3H_X3_CLAIM_SIMD)
         dwx_put(TA3, 256, 16 * wave + 4 * (lane >> 4), lane & 15, ra[0]);
         dwx_put(TA3, 256, 16 * (wave + 8) + 4 * (lane >> 4), lane & 15, ra[1]);
         dwx_put(TB3, 128, 16 * wave + 4 * (lane >> 4), lane & 15, rbv);
-#endif
         const bool bias_now = want_db && db && (!dz2 || t >= n16);
         __syncthreads();
         if (t + (int)gridDim.x < ngroups) issue(t + gridDim.x);
@@ -1156,9 +1076,6 @@ __global__ __launch_bounds__(512) void sdf_mlp_bwd_dw_layers_x3_kernel(const flo
                 A[a][pl] = *(const u32x4*)(TA3 + (pl * 256 + (rg * 2 + a) * 32 + i) * DWX_PITCH + 4 * h);
                 B[a][pl] = *(const u32x4*)(TB3 + (pl * 128 + (cg * 2 + a) * 32 + i) * DWX_PITCH + 4 * h);
             }
-#ifdef D3H_DWX_PROBE_NOMFMA
-        acc[0][0][0] += __uint_as_float(A[0][0][0] ^ B[0][0][0] ^ A[1][NP - 1][3] ^ B[1][NP - 1][3]) * 0.f;
-#else
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
 #pragma unroll
@@ -1178,13 +1095,8 @@ __global__ __launch_bounds__(512) void sdf_mlp_bwd_dw_layers_x3_kernel(const flo
                 accdb[a] = D3H_MFMA32_BF16X8(A[a][0], ones, accdb[a]);
             }
         }
-#endif
         __syncthreads();
     }
-#endif
-#ifdef D3H_DWX_PROBE_NOFLUSH
-    if (acc[0][0][0] != 12345.678f) return;
-#endif
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
 #pragma unroll
@@ -1216,8 +1128,8 @@ __global__ __launch_bounds__(512) void sdf_mlp_bwd_dw_layers_x3_kernel(const flo
 // 10^-2 and keep the residual plane scaled); the sums are multiplied by 1 / (64 s) at the flush.  Products a_m b_m are dropped: 2^-22 relative.
 constexpr float DWH_US = 64.0f;
 __device__ __forceinline__ void dwh_split_pair(float a, float b, unsigned& h, unsigned& m) {
-    h = h2_pk(a, b);
-    m = h2_pk(a - h2_lo(h), b - h2_hi(h));
+    h = d3h_h2_pk(a, b);
+    m = d3h_h2_pk(a - d3h_h2_lo(h), b - d3h_h2_hi(h));
 }
 // four features f0 .. f0 + 3 of point j (one tile-packed f32x4), times sc -> T[plane 2][feature][pair word j / 2]
 __device__ __forceinline__ void dwh_put(unsigned* T, int nrows, int f0, int j, f32x4 v, float sc) {
@@ -1534,8 +1446,8 @@ extern "C" int d3h_sdf_mlp_bwd_prepare(const float* x, const float* deform, floa
 // tile_list: int scratch of (n + 15) / 16 + 1 entries, or NULL.  When given, the backward runs only over the 16-point tiles that
 // contain a non-zero gout (exact: the others contribute zero to every output) -- the normal case of a training sweep, where the loss
 // reads the sdf only next to the extracted surface.
-// wpack3_recompute: NULL = `act` holds the activations of the forward (d3h_sdf_mlp_fwd* with the save).  Otherwise (d3h_sdf_mlp_pack3 of the same
-// weights) the forward ran WITHOUT the save and `act` is scratch of d3h_sdf_mlp_act_floats(n) floats: the activations the backward needs are
+// wpack3_recompute: NULL = `act` holds the activations of the forward (d3h_sdf_mlp_fwd* with the save).  Otherwise (d3h_sdf_mlp_pack3 or
+// d3h_sdf_mlp_pack_h2 of the same weights, see recompute_planes) the forward ran WITHOUT the save and `act` is scratch of d3h_sdf_mlp_act_floats(n) floats: the activations the backward needs are
 // recomputed here first.  With tile_list (then an int scratch of d3h_sdf_mlp_bwd_scratch_ints(n) entries) the backward runs in the COMPACT form:
 // the points with a non-zero gout are gathered into dense 16-point tiles (see sdf_mlp_active_points_kernel) and only those are recomputed and
 // back-propagated: ~3 % of a grid sweep instead of a 1.88 GB store in the forward of which ~15 % was read back.
@@ -1692,7 +1604,7 @@ int d3h_sdf_mlp_jvp_x3_launch(const float* x, const float* udir, const unsigned*
 
 // g[n][3] = d(sdf)/d(x) from the saved activations of a forward with save; fills dz (tile-packed dZ_l, kept for d3h_sdf_mlp_eik_bwd)
 // (max_cus: as d3h_sdf_mlp_fwd)
-// wpackT3: optional (d3h_sdf_mlp_pack_t3 of the same weights): the sweep then runs on the bf16 matrix pipe (sdf_mlp_x3.h) and wpackT may be NULL
+// wpackT3: optional (d3h_sdf_mlp_pack_t3 or d3h_sdf_mlp_pack_t_h2 of the same weights): the sweep then runs on split operands (sdf_mlp_x3.h) and wpackT may be NULL
 // t_planes: what wpackT3 is -- 3 = d3h_sdf_mlp_pack_t3 (bf16 x 3), 2 = d3h_sdf_mlp_pack_t_h2 (fp16 x 2; d(sdf) = 1 here, so the operand scale is a constant)
 extern "C" int d3h_sdf_mlp_grad_x(const float* x, const float* w7, const float* wpackT, const unsigned* wpackT3, int t_planes, const float* act, float* dz,
                                   int64_t n, float* g, int max_cus, void* stream) {
@@ -1727,8 +1639,8 @@ extern "C" int d3h_eikonal_loss(const float* g, int64_t n, float scale, float* l
 // Weight gradients of sum_p <u_p, grad_x f(x_p)> ACCUMULATED into dw0 .. dw7 (layouts as d3h_sdf_mlp_bwd; there is no db7 term).
 // act / dz: from d3h_sdf_mlp_fwd(save) / d3h_sdf_mlp_grad_x on the same x; tb, eb: scratch of d3h_sdf_mlp_act_floats(n) floats each.
 // max_cus: as d3h_sdf_mlp_fwd (the two sweeps; the weight-gradient GEMMs keep their split-K grids).
-// wpack3 / wpackT3: optional (d3h_sdf_mlp_pack3 / d3h_sdf_mlp_pack_t3 of the same weights): the tangent / reverse sweep then runs on the
-// bf16 matrix pipe (sdf_mlp_x3.h) and the f32 pack it replaces may be NULL.
+// wpack3 / wpackT3: optional (a split-plane pack of the same weights, forward / transposed form): the tangent / reverse sweep then runs on
+// split operands of that kind (sdf_mlp_x3.h) and the f32 pack it replaces may be NULL.
 // f_planes / t_planes: what wpack3 / wpackT3 are (3: d3h_sdf_mlp_pack3 / d3h_sdf_mlp_pack_t3, 2: d3h_sdf_mlp_pack_h2 / d3h_sdf_mlp_pack_t_h2).
 // u_hint (needed when either is 2): the magnitude of the entries of udir, to within a factor of ~30 either way -- the h2 sweeps scale their
 // operands by a power of two derived from it (tangents ~10 |u|, injected curvature terms ~10^2 |u|); for the eikonal loss: 2 * coeff / n.

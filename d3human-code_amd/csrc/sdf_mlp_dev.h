@@ -91,14 +91,7 @@ __device__ __forceinline__ void glds_commit() {
 #ifndef D3H_SDF_GLDS
 #define D3H_SDF_GLDS 1
 #endif
-#if defined(D3H_PROBE_NO_STAGE)          // tools/probe/sdf_variants.sh: timing experiments only (results are garbage)
-#define SDF_STAGE_ISSUE(st, src, dst, n4, tid) ((void)0)
-#if defined(D3H_PROBE_NO_BARRIER)
-#define SDF_STAGE_COMMIT(st, dst, n4, tid) ((void)0)
-#else
-#define SDF_STAGE_COMMIT(st, dst, n4, tid) __syncthreads()
-#endif
-#elif D3H_SDF_GLDS
+#if D3H_SDF_GLDS
 #define SDF_STAGE_ISSUE(st, src, dst, n4, tid) glds_issue(src, dst, n4, tid)
 #define SDF_STAGE_COMMIT(st, dst, n4, tid) glds_commit()
 #else

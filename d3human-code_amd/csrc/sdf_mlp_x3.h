@@ -23,6 +23,7 @@
 //   layer 4 (net.8, skip)         8 chunks of [rbl 2][kb 8 + EMB_KB][part 3][lane 64][4]       (kb >= 8: embedding)
 //   tail (fp32): bias0..bias6, W7, b7 exactly as in wpack
 #pragma once
+#include "d3h_h2.h"
 #include "sdf_mlp_dev.h"
 
 namespace D3H_MLP_NS {
@@ -117,12 +118,6 @@ __device__ __forceinline__ void x3_split_pair(float a, float b, unsigned& h, uns
 }
 // two D blocks (features 32 kb + 4 q + r and 32 kb + 16 + 4 q + r) -> the B operand triple of k-block kb
 __device__ __forceinline__ void x3_split_blocks(const f32x4 v0, const f32x4 v1, u32x4 (&out)[3]) {
-#ifdef D3H_X3_PROBE_NOSPLIT       // (timing probe; results are wrong)
-    out[0] = u32x4{__float_as_uint(v0[0]), __float_as_uint(v0[1]), __float_as_uint(v0[2]), __float_as_uint(v0[3])};
-    out[1] = u32x4{__float_as_uint(v1[0]), __float_as_uint(v1[1]), __float_as_uint(v1[2]), __float_as_uint(v1[3])};
-    out[2] = out[0];
-    return;
-#endif
     unsigned h[4], m[4], l[4];
     x3_split_pair(v0[0], v0[1], h[0], m[0], l[0]);
     x3_split_pair(v0[2], v0[3], h[1], m[1], l[1]);
@@ -152,28 +147,19 @@ __device__ __forceinline__ void x3_mac(f32x4& acc, const u32x4 a0, const u32x4 a
 // (unscaled, every residual of an operand below 0.12 would be subnormal: measured 2 x the error); the two cross products are accumulated
 // apart (`lo`) and folded in once per 16-row block: acc = hi + 2^-11 lo.  fp16 has 5 exponent bits: operands above 65 504 overflow -- the
 // network's activations and weights are O(1) (softplus of a unit-scale SDF); the pack kernel refuses (NaN-fills) weights above 2^14, and the
-// sweeps whose operands have no natural scale (gradients: the data-backward and weight-gradient kernels) stay on the bf16 x 3 split.
+// sweeps whose operands have no natural scale (gradients: the data-backward and weight-gradient kernels) scale them by a power of two per
+// launch (h2_grad_scale below); each can be kept on the bf16 x 3 split instead (D3H_SDF_H2_BWD=0, D3H_DW_H2=0).
 constexpr float H2_SCALE = 2048.0f, H2_INV_SCALE = 1.0f / 2048.0f;
+// (the packed-f16 conversions d3h_h2_pk / d3h_h2_lo / d3h_h2_hi are those of d3h_h2.h: v_cvt_pk_f16_f32, round to nearest even)
 #ifndef D3H_EMULATED
-typedef _Float16 d3h_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 d3h_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned h2_pk(float lo, float hi) {
-    d3h_f16x2 v = {(_Float16)lo, (_Float16)hi};          // v_cvt_pk_f16_f32: round to nearest even
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float h2_lo(unsigned u) { return (float)__builtin_bit_cast(d3h_f16x2, u)[0]; }
-__device__ __forceinline__ float h2_hi(unsigned u) { return (float)__builtin_bit_cast(d3h_f16x2, u)[1]; }
 #define D3H_MFMA_F16X8(a, b, c) \
-    __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(d3h_f16x8, a), __builtin_bit_cast(d3h_f16x8, b), c, 0, 0, 0)
+    __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(d3h_h2_f16x8, a), __builtin_bit_cast(d3h_h2_f16x8, b), c, 0, 0, 0)
 #else
-__device__ __forceinline__ unsigned h2_pk(float lo, float hi) { return emul::f32_to_f16_bits(lo) | (emul::f32_to_f16_bits(hi) << 16); }
-__device__ __forceinline__ float h2_lo(unsigned u) { return emul::f16_bits_to_f32(u & 0xffffu); }
-__device__ __forceinline__ float h2_hi(unsigned u) { return emul::f16_bits_to_f32(u >> 16); }
 #define D3H_MFMA_F16X8(a, b, c) emul::mfma_16x16x32f16(a, b, c)
 #endif
 __device__ __forceinline__ void h2_split_pair(float a, float b, unsigned& h, unsigned& m) {
-    h = h2_pk(a, b);
-    m = h2_pk((a - h2_lo(h)) * H2_SCALE, (b - h2_hi(h)) * H2_SCALE);
+    h = d3h_h2_pk(a, b);
+    m = d3h_h2_pk((a - d3h_h2_lo(h)) * H2_SCALE, (b - d3h_h2_hi(h)) * H2_SCALE);
 }
 
 // operand planes of two D blocks, any plane count
@@ -215,9 +201,6 @@ __device__ __forceinline__ void xp_split_blocks(const f32x4 v0, const f32x4 v1, 
 
 // ---- weight-chunk staging and the k-loop of one 16-row output block (shared by the forward and the data-backward kernels) ----------
 __device__ __forceinline__ void x3_issue(const unsigned* __restrict__ src, unsigned* dst, int n4, int tid) {
-#ifdef D3H_X3_PROBE_NOSTAGE       // (timing probe: no weight stream; results are wrong)
-    return;
-#endif
     const int wave_base = tid & ~63;
 #pragma unroll
     for (int i = 0; i < X3_STAGE_F4; ++i) {
@@ -241,10 +224,7 @@ __device__ __forceinline__ void x3_mac_blocks(f32x4& acc, const u32x4 (&xs)[NKB]
     for (int kb = 0; kb < NKB; ++kb) {
         if (kb == MID) mid();
         const unsigned* pn = p + (kb + 1) * 3 * X3_FRAG;
-#if defined(D3H_X3_PROBE_NOLDS)     // (timing probe: one set of fragments per block; results are wrong)
-        x3_mac(acc, a0, a1, a2, xs[kb]);
-        (void)pn;
-#elif D3H_X3_MAC == 0
+#if D3H_X3_MAC == 0
         acc = D3H_MFMA_BF16X8(a2, xs[kb][0], acc);
         if (kb + 1 < NKB) a2 = *(const u32x4*)(pn + 2 * X3_FRAG);
         acc = D3H_MFMA_BF16X8(a1, xs[kb][1], acc);

@@ -86,9 +86,6 @@ namespace {
 
 // bias + softplus in place on one 16-feature block; optional tile-packed save for the backward pass (sdf_mlp.hip: epilogue)
 __device__ __forceinline__ void x3_epilogue(f32x4& v, const float* bias_l, int rb, int lane, float* act_tile_layer) {
-#ifdef D3H_X3_PROBE_NOEPI
-    return;
-#endif
     f32x4 b = *(const f32x4*)(bias_l + 16 * rb + 4 * (lane >> 4));
     f32x4 o;
 #pragma unroll
@@ -269,13 +266,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void sdf_mlp_fwd_x3_kernel(const float
                             }
                         }
                     });
-#ifndef D3H_X3_PROBE_NOSKIP      // (timing probe: what the 24 registers of E3 cost inside the layer loop; results are wrong)
                     if (skip) xp_mac_blocks<NP, X3_EMB_KB, -1>(acc0, lo0, E3, wl + 8 * NP * X3_FRAG, lane, X3None());      // mlp.py:40-41 cat([x, emb])
-#endif
                     xp_mac_blocks<NP, 8, -1>(acc1, lo1, Xs, wl + rstride, lane, X3None());
-#ifndef D3H_X3_PROBE_NOSKIP
                     if (skip) xp_mac_blocks<NP, X3_EMB_KB, -1>(acc1, lo1, E3, wl + rstride + 8 * NP * X3_FRAG, lane, X3None());
-#endif
                     Y[2 * c] = xp_fold<NP>(acc0, lo0);
                     Y[2 * c + 1] = xp_fold<NP>(acc1, lo1);
                 }

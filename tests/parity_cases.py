@@ -32,8 +32,7 @@ def check_sdf_mlp_forward(dev, n=None, tol=2e-7, x3=False):
     ref = g['sdf'].reshape(-1)
     if n is not None:
         x, ref = x[:n].contiguous(), ref[:n]
-    wp = sdf_mlp.pack_weights(sd)
-    out = sdf_mlp.forward(x, wp, wp3=sdf_mlp.pack_weights3(sd) if x3 else None).cpu().numpy()
+    out = sdf_mlp.forward(x, sdf_mlp.pack_weights(sd, 'bf16x3' if x3 else 'f32')).cpu().numpy()
     err = np.abs(out - ref).max()
     assert err < tol, f'sdf max abs err {err}'
     # topology is decided by sdf > 0 (gshell_tets.py:260): signs must agree wherever |sdf_ref| > tau

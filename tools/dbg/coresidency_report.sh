@@ -1,8 +1,8 @@
 #!/bin/bash
 # The co-residency hazard of the bf16-MFMA weight-gradient kernel, as counts: ticks (of 96 per line) whose gradients differ
 # from the first tick of the same scene state, for the default build and for builds in which the kernel shares its SIMDs with other kernels.
-#   bash tools/build_variant.sh share -DD3H_DWX_SHARE_SIMDS; ... share_nowork / share_noflush likewise;  gpurun -- 'bash tools/dbg/coresidency_report.sh'
-for v in hip share share_nowork share_noflush; do
+#   bash tools/build_variant.sh share -DD3H_DWX_SHARE_SIMDS;  then, on a machine with the GPU:  bash tools/dbg/coresidency_report.sh
+for v in hip share; do
   for i in 1 2; do
     n=$(D3H_LIB_PATH=$PWD/d3human-code_amd/d3h/libd3h_$v.so python tools/dbg/gpu_dbg_x3_race.py 48 2>&1 | grep -c "bad: \[(")
     echo "build $v run $i: $n of 96 ticks differ"
