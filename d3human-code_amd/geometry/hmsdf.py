@@ -176,6 +176,8 @@ class HmSDFTetsGeometry(torch.nn.Module):
         self.sdf_net = MLP(skip_in=_flag(F_, 'skip_in', [3]), n_freq=_flag(F_, 'n_freq', 6), n_hidden=_flag(F_, 'n_hidden', 6),
                            d_hidden=_flag(F_, 'd_hidden', 256), use_float16=_flag(F_, 'use_float16', False)).to(self.device)
         self.smplx_deform.initialize(betas=F_.shape_param.to(self.device))
+        if _flag(F_, 'tet_smpl', False):
+            self._init_tet_smpl()
         steps = _flag(F_, 'sdf_mlp_pretrain_smpl_steps', 3000)
         ckp = None
         if _flag(F_, 'out_dir'):
@@ -189,10 +191,7 @@ class HmSDFTetsGeometry(torch.nn.Module):
             # hmsdf.py:236-237: sdf_gt = -pysdf.SDF(template verts, faces)(grid verts).  Here: the same quantity (exact distance,
             # containment sign, positive outside) from the brute-force GPU kernel d3h_mesh_sdf -- no CPU third party at start-up.
             from d3h import meshops as _MO
-            if self.smplx_deform.layer.faces is None:
-                raise RuntimeError('HmSDFTetsGeometry: the SDF pre-fit needs a body model with faces (the SMPL-X template mesh, '
-                                   'hmsdf.py:232-237) or FLAGS.sdf_init_fn (an analytic target, as the synthetic scenes use)')
-            faces = torch.as_tensor(np.asarray(self.smplx_deform.layer.faces).astype(np.int64), device=self.device)
+            faces = self._template_faces()
             sdf_gt = _MO.mesh_sdf(self.verts, self.smplx_deform.vs_template[0].detach(), faces).reshape(-1, 1)
         else:
             sdf_gt = fn(self.verts).reshape(-1, 1).to(self.device)
@@ -207,6 +206,41 @@ class HmSDFTetsGeometry(torch.nn.Module):
             self.sdf_prefit_loss = float(loss.detach())
         if ckp:
             torch.save(self.sdf_net.state_dict(), ckp)
+
+    def _template_faces(self):
+        if self.smplx_deform.layer.faces is None:
+            raise RuntimeError('HmSDFTetsGeometry: the SDF pre-fit needs a body model with faces (the SMPL-X template mesh, '
+                               'hmsdf.py:232-237) or FLAGS.sdf_init_fn (an analytic target, as the synthetic scenes use)')
+        return torch.as_tensor(np.asarray(self.smplx_deform.layer.faces).astype(np.int64), device=self.device)
+
+    def _init_tet_smpl(self):
+        """hmsdf.py:239-249 (FLAGS.tet_smpl; off: none of this exists): the tet mesh of the SMPL-X template, its signed distance, its edges and the
+        `smpl_msdf` parameter.  get_tet_mesh's tetgen is replaced by d3h.tetfill.fill_mesh -- a lattice of FLAGS.tet_smpl_res (64) cells per side
+        clipped by the template's signed distance, built on the device from vs_template -- and pysdf by d3h.meshops.mesh_sdf
+        (positive outside, as sdf_gt).  The one random draw stands where the reference makes it: after the SDF network is constructed, before its
+        pre-fit or checkpoint load.  No loss reads any of it (the reference has none either) and the parameter never receives a gradient."""
+        from d3h import meshops as _MO
+        from d3h import tetfill as _TF
+        F_ = self.FLAGS
+        faces = self._template_faces()
+        template = self.smplx_deform.vs_template[0].detach().float().contiguous()
+        with torch.no_grad():
+            v, t, _ = _TF.fill_mesh(template, faces, res=int(_flag(F_, 'tet_smpl_res', 64)), scale=1.1)
+            if _flag(F_, 'out_dir'):
+                os.makedirs(F_.out_dir, exist_ok=True)
+                np.savez(os.path.join(F_.out_dir, 'smpl_template_tet_{}.npz'.format(self.grid_res)), v=v.cpu().numpy(), f=t.cpu().numpy())
+            self.tet_smpl_v, self.tet_smpl_f = v, t
+            self.sdf_tet_gt = _MO.mesh_sdf(v, template, faces).reshape(-1, 1)
+            self.generate_edges_smpl()
+            msdf = (torch.rand_like(self.tet_smpl_v[:, 0]) - 0.01).clamp(-1, 1)          # hmsdf.py:247
+        self.smpl_msdf = torch.nn.Parameter(msdf.clone().detach(), requires_grad=True)
+
+    @torch.no_grad()
+    def generate_edges_smpl(self):
+        """hmsdf.py:391-397"""
+        e = self.tet_smpl_f[:, [0, 1, 0, 2, 0, 3, 1, 2, 1, 3, 2, 3]].reshape(-1, 2)
+        self.all_edges_smpl = torch.unique(torch.sort(e, dim=1)[0], dim=0)
+        self.max_displacement_smpl = 1.0 / self.grid_res * self.scale / 2.1
 
     def _init_use_nonrigid_deform(self):
         if not _flag(self.FLAGS, 'use_nonrigid_deform', False):

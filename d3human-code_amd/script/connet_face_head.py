@@ -4,8 +4,8 @@ the component labelling and the vertex weld run on the device (d3h/meshtopo.py, 
 `set.issubset` loops.
 
 This directory has no __init__.py on purpose: `script` is a namespace package in the reference too, so with both roots on the path
-`script.connet_face_head` and `script.process_body_cloth_head_msdfcut` resolve here while `script.get_tet_smpl` keeps resolving to the
-reference's file.
+`script.connet_face_head`, `script.process_body_cloth_head_msdfcut` and `script.get_tet_smpl` resolve here while any other `script` module keeps
+resolving to the reference's file.
 
 Deviations from the reference:
   * openmesh may drop faces it finds non-manifold when it loads a file; here every `f` line is kept;
