@@ -1764,6 +1764,287 @@ __global__ __launch_bounds__(256) void aa_composite_bwd_kernel(CompArgs a, const
     }          // sub-tile loop
 }
 
+// ---- one step of layered compositing (depth peeling, render/render.py:375-382 with more than one layer) ---------------------------------
+// Layers are blended back to front; one step lays layer l over the image `under` [npix][C] of what lies behind it and antialiases the
+// result along layer l's silhouettes:
+//     pre[p]  = lerp(under[p], [src_k[p], 1], w[p])  per buffer k,   w[p] = covered_l(p) * alpha[p]   (alpha NULL: 1)
+//     out     = antialias(pre, rast_l, pos, tri)
+// kind 3 (the alpha-only 'msdf_image', one channel): pre = lerp(under, 1, covered * src); `alpha` does not enter.  The other kinds differ only in
+// the background the host wrote into the deepest `under`; here they are one case.  The lerp is torch.lerp's two-branch form, exact at w = 0
+// (under) and w = 1 (the source), so a layer that covers nothing is the identity.  Same shape as the fused pair above: pre[p] is a function
+// of pixel p alone, so phase 2 re-evaluates the pair's other pixel and no pre-antialias image is stored.
+__device__ __forceinline__ float layer_lerp(float a, float b, float w) { return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.0f - w); }
+
+// pre-antialias value of channel j of source c at global pixel i; u = under + i * C + (first channel of the source), w = covered * alpha
+__device__ __forceinline__ float layer_value(const CompSrc& c, int j, size_t i, bool cov, float w, const float* __restrict__ u) {
+    if (!cov) return u[j];
+    if (c.kind == 3) return layer_lerp(u[0], 1.0f, c.p[i * c.stride]);
+    return layer_lerp(u[j], j < c.nch ? c.p[i * c.stride + j] : 1.0f, w);
+}
+
+__global__ __launch_bounds__(256) void layer_composite_fwd_kernel(CompArgs a, const float* __restrict__ alpha, const float* __restrict__ under,
+                                                                  const float* __restrict__ rast, const float* __restrict__ pos, int pos_bstride,
+                                                                  const int* __restrict__ tri, const unsigned char* __restrict__ flags, int nf, int nb,
+                                                                  int H, int W, float* __restrict__ out) {
+    D3H_DYN_SHARED(float, lay_lds);           // 256 * C floats: the rows of `under`, blended in place
+    const size_t hw = (size_t)H * W;
+    const size_t n = (size_t)nb * hw;
+    const size_t p0 = (size_t)blockIdx.x * AA_WG_PIX;
+    const int C = a.C;
+    for (int st = 0; st < AA_TILES; ++st) {
+        const size_t first = p0 + (size_t)st * 256;
+        if (first >= n) break;                                   // (workgroup-uniform)
+        const size_t i = first + threadIdx.x;
+        block_load_rows(lay_lds, under, first, n, C);
+        if (i < n && rast[4 * i + 3] > 0.f) {
+            const float w = alpha ? alpha[i] : 1.0f;
+            float* o = lay_lds + (size_t)threadIdx.x * C;
+            for (int k = 0; k < a.n; ++k) {
+                const CompSrc& c = a.s[k];
+                const int wch = c.kind == 3 ? 1 : c.nch + 1;
+                for (int j = 0; j < wch; ++j) o[j] = layer_value(c, j, i, true, w, o);
+                o += wch;
+            }
+        }
+        block_store_rows(out, lay_lds, first, n, C);
+    }
+    __syncthreads();                       // phase 2 overwrites pixels phase 1 (other threads of this workgroup) has just written
+    for (int st = 0; st < AA_TILES; ++st) {
+        const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
+        int b = 0, x = 0, y = 0;
+        if (i < n) {
+            b = (int)(i / hw);
+            const int rem = (int)(i % hw);
+            y = rem / W; x = rem % W;
+        }
+        const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);
+        if (!work) continue;
+        const float* rast_b = rast + 4 * (size_t)b * hw;
+        const float* posb = pos + (size_t)b * pos_bstride;
+        const unsigned char* flags_b = flags + (size_t)b * nf;
+        const size_t gb = (size_t)b * hw;                         // global pixel index of the frame's first pixel
+        const int self = y * W + x;
+        AAPair pr[4];
+        bool cov_o[4];
+        float w_o[4];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
+            pr[k].ok = pr[k].ok && pr[k].self_is_dst && pr[k].wgt != 0.f;
+            cov_o[k] = pr[k].ok ? rast_b[4 * (size_t)pr[k].other + 3] > 0.f : false;
+            w_o[k] = (cov_o[k] && alpha) ? alpha[gb + pr[k].other] : 1.0f;
+            any |= pr[k].ok;
+        }
+        if (!any) continue;
+        const bool cov_s = rast_b[4 * (size_t)self + 3] > 0.f;
+        const float w_s = (cov_s && alpha) ? alpha[gb + self] : 1.0f;
+        float* orow = out + (gb + self) * C;
+        int off = 0;
+        for (int s_ = 0; s_ < a.n; ++s_) {
+            const CompSrc& c = a.s[s_];
+            const int wch = c.kind == 3 ? 1 : c.nch + 1;
+            for (int j = 0; j < wch; ++j) {
+                const float base = layer_value(c, j, gb + self, cov_s, w_s, under + (gb + self) * C + off);
+                float v = base;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (pr[k].ok) v += pr[k].wgt * (layer_value(c, j, gb + pr[k].other, cov_o[k], w_o[k], under + (gb + pr[k].other) * C + off) - base);
+                orow[off + j] = v;
+            }
+            off += wch;
+        }
+    }
+}
+
+// Backward of the step.  Phase 1: every pixel as if no pair touched it (g = g_out[p]); the rows of g_out are staged in LDS and turned into
+// the rows of d(under) in place, each source's block leaves through `outb` as in aa_composite_bwd_kernel, d(alpha) is one coalesced float per
+// pixel.  `under` is read per lane (C consecutive floats of the lane's pixel) and only where alpha or a kind-3 source takes a gradient.  Phase 2:
+// the pixels on an id discontinuity gather their pre-antialias gradient (as aa_bwd_kernel) and rewrite their own entries; the owner of a pair
+// adds the pair's position gradient.  No atomics but those of d_pos.  dsrc[k], d_alpha, d_under may each be NULL: not written.
+__global__ __launch_bounds__(256) void layer_composite_bwd_kernel(CompArgs a, const float* __restrict__ alpha, const float* __restrict__ under,
+                                                                  const float* __restrict__ rast, const float* __restrict__ pos, int pos_bstride,
+                                                                  const int* __restrict__ tri, const unsigned char* __restrict__ flags, int nf, int nb,
+                                                                  int H, int W, const float* __restrict__ g_out, float* __restrict__ d_alpha,
+                                                                  float* __restrict__ d_under, float* __restrict__ d_pos) {
+    D3H_DYN_SHARED(float, lb_lds);            // 256 * C floats (rows of g_out -> rows of d_under) + 256 * max(dch) floats (one source's block on its way out)
+    const size_t hw = (size_t)H * W;
+    const size_t n = (size_t)nb * hw;
+    const size_t p0 = (size_t)blockIdx.x * AA_WG_PIX;
+    const int C = a.C;
+    float* rows = lb_lds;
+    float* outb = lb_lds + 256 * C;
+    for (int st = 0; st < AA_TILES; ++st) {
+        const size_t first = p0 + (size_t)st * 256;
+        if (first >= n) break;                                   // (workgroup-uniform)
+        const size_t i = first + threadIdx.x;
+        const bool cov = i < n ? rast[4 * i + 3] > 0.f : false;
+        const float w = cov ? (alpha ? alpha[i] : 1.0f) : 0.f;
+        block_load_rows(rows, g_out, first, n, C);
+        float* gi = rows + (size_t)threadIdx.x * C;
+        const float* u = under + (i < n ? i : 0) * C;
+        int off = 0;
+        float da = 0.f;
+        for (int k = 0; k < a.n; ++k) {
+            const CompSrc& c = a.s[k];
+            const int wch = c.kind == 3 ? 1 : c.nch + 1;
+            if (i < n) {
+                float* ob = outb + threadIdx.x * c.dch;
+                if (c.kind == 3) {
+                    if (c.d) ob[0] = cov ? gi[off] * (1.0f - u[off]) : 0.f;
+                    if (d_under) gi[off] = gi[off] * (1.0f - (cov ? c.p[i * c.stride] : 0.f));
+                } else {
+                    for (int j = 0; j <= c.nch; ++j) {
+                        const float gv = gi[off + j];
+                        if (j < c.nch && c.d) ob[j] = gv * w;
+                        if (d_alpha && cov) da += gv * ((j < c.nch ? c.p[i * c.stride + j] : 1.0f) - u[off + j]);
+                        if (d_under) gi[off + j] = gv * (1.0f - w);
+                    }
+                }
+                if (c.d) for (int j = c.kind == 3 ? 1 : c.nch; j < c.dch; ++j) ob[j] = 0.f;
+            }
+            if (c.d) block_store_rows(c.d, outb, first, n, c.dch);     // (workgroup-uniform)
+            off += wch;
+        }
+        if (d_alpha && i < n) d_alpha[i] = da;
+        if (d_under) block_store_rows(d_under, rows, first, n, C);
+    }
+    __syncthreads();                       // phase 2 overwrites entries phase 1 (other threads of this workgroup) has just written
+    for (int st = 0; st < AA_TILES; ++st) {
+    const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
+    int b = 0, x = 0, y = 0;
+    if (i < n) {
+        b = (int)(i / hw);
+        const int rem = (int)(i % hw);
+        y = rem / W; x = rem % W;
+    }
+    const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);
+    if (!work) continue;
+    const float* rast_b = rast + 4 * (size_t)b * hw;
+    const float* posb = pos + (size_t)b * pos_bstride;
+    const unsigned char* flags_b = flags + (size_t)b * nf;
+    const size_t gb0 = (size_t)b * hw;                            // global pixel index of the frame's first pixel
+    const float* gb = g_out + gb0 * C;
+    const int self = y * W + x;
+    AAPair pr[4];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
+        any |= pr[k].ok;
+    }
+    if (!any) continue;
+    // ---- this pixel's gradients again, from the gathered gradient of its pre-antialias row ----
+    {
+        bool touch = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (pr[k].ok && pr[k].wgt != 0.f) touch = true;
+        if (touch) {
+            const bool cov_s = rast_b[4 * (size_t)self + 3] > 0.f;
+            const float w_s = cov_s ? (alpha ? alpha[gb0 + self] : 1.0f) : 0.f;
+            const float* u = under + (gb0 + self) * C;
+            int off = 0;
+            float da = 0.f;
+            for (int s_ = 0; s_ < a.n; ++s_) {
+                const CompSrc& c = a.s[s_];
+                const int wch = c.kind == 3 ? 1 : c.nch + 1;
+                for (int j = 0; j < wch; ++j) {
+                    const float gs = gb[(size_t)self * C + off + j];
+                    float v = gs;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if (!pr[k].ok || pr[k].wgt == 0.f) continue;
+                        if (pr[k].self_is_dst) v -= pr[k].wgt * gs;
+                        else v += pr[k].wgt * gb[(size_t)pr[k].other * C + off + j];
+                    }
+                    if (c.kind == 3) {
+                        if (c.d) c.d[(gb0 + self) * c.dch] = cov_s ? v * (1.0f - u[off]) : 0.f;
+                        if (d_under) d_under[(gb0 + self) * C + off] = v * (1.0f - (cov_s ? c.p[(gb0 + self) * c.stride] : 0.f));
+                    } else {
+                        if (j < c.nch && c.d) c.d[(gb0 + self) * c.dch + j] = v * w_s;
+                        if (d_alpha && cov_s) da += v * ((j < c.nch ? c.p[(gb0 + self) * c.stride + j] : 1.0f) - u[off + j]);
+                        if (d_under) d_under[(gb0 + self) * C + off + j] = v * (1.0f - w_s);
+                    }
+                }
+                off += wch;
+            }
+            if (d_alpha) d_alpha[gb0 + self] = da;
+        }
+    }
+    // ---- position gradient of the two pairs this pixel owns ----
+    if (!d_pos) continue;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!pr[k].ok) continue;
+        const int dirx = (k == 0) ? 1 : 0;
+        const AAHit h = aa_analyse(rast_b, posb, tri, flags_b, x, y, dirx, H, W);      // (analysed again: see aa_bwd_kernel)
+        if (!h.ok) continue;
+        const float alpha_d = h.d - 0.5f;
+        if (alpha_d == 0.f) continue;                                                 // (see aa_bwd_kernel)
+        const int dst = (alpha_d >= 0.f) ? h.po : h.pi;
+        const int src = (alpha_d >= 0.f) ? h.pi : h.po;
+        const bool cov_src = rast_b[4 * (size_t)src + 3] > 0.f, cov_dst = rast_b[4 * (size_t)dst + 3] > 0.f;
+        const float w_src = (cov_src && alpha) ? alpha[gb0 + src] : 1.0f, w_dst = (cov_dst && alpha) ? alpha[gb0 + dst] : 1.0f;
+        float gw = 0.f;
+        {
+            int off = 0;
+            for (int s_ = 0; s_ < a.n; ++s_) {
+                const CompSrc& c = a.s[s_];
+                const int wch = c.kind == 3 ? 1 : c.nch + 1;
+                for (int j = 0; j < wch; ++j) {
+                    const float g = gb[(size_t)dst * C + off + j];
+                    if (g != 0.f) gw = fmaf(g, layer_value(c, j, gb0 + src, cov_src, w_src, under + (gb0 + src) * C + off)
+                                               - layer_value(c, j, gb0 + dst, cov_dst, w_dst, under + (gb0 + dst) * C + off), gw);
+                }
+                off += wch;
+            }
+        }
+        if (gw == 0.f) continue;
+        const float gd = (alpha_d > 0.f) ? gw : -gw;
+        float px_i = (float)(h.pi % W) + 0.5f, py_i = (float)(h.pi / W) + 0.5f;
+        float px_o = (float)(h.po % W) + 0.5f, py_o = (float)(h.po / W) + 0.5f;
+        int vv[2] = {h.va, h.vb};
+        float4 pc[2];
+        float qv[2], ex[2], ey[2];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            pc[kk] = *(const float4*)(posb + 4 * (size_t)vv[kk]);
+            qv[kk] = 1.0f / pc[kk].w;
+            ex[kk] = (pc[kk].x * qv[kk] * 0.5f + 0.5f) * W;
+            ey[kk] = (pc[kk].y * qv[kk] * 0.5f + 0.5f) * H;
+        }
+        float gsx[2], gsy[2];
+        if (dirx) {
+            float ge = gd / (px_o - px_i);
+            float dy = ey[1] - ey[0];
+            float tt = (py_i - ey[0]) / dy;
+            float gtt = ge * (ex[1] - ex[0]);
+            gsx[0] = ge * (1.f - tt); gsx[1] = ge * tt;
+            gsy[0] = gtt * (tt - 1.f) / dy;
+            gsy[1] = -gtt * tt / dy;
+        } else {
+            float ge = gd / (py_o - py_i);
+            float dx = ex[1] - ex[0];
+            float tt = (px_i - ex[0]) / dx;
+            float gtt = ge * (ey[1] - ey[0]);
+            gsy[0] = ge * (1.f - tt); gsy[1] = ge * tt;
+            gsx[0] = gtt * (tt - 1.f) / dx;
+            gsx[1] = -gtt * tt / dx;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            float q = qv[kk];
+            float gX = gsx[kk] * 0.5f * W, gY = gsy[kk] * 0.5f * H;
+            float* dp = d_pos + (size_t)b * pos_bstride + 4 * (size_t)vv[kk];
+            atomicAdd(dp + 0, gX * q);
+            atomicAdd(dp + 1, gY * q);
+            atomicAdd(dp + 3, -(gX * pc[kk].x + gY * pc[kk].y) * q * q);
+        }
+    }
+    }          // sub-tile loop
+}
+
 // ------------------------------------------------------------------------------------------------
 // texture (2-D, bilinear, clamp)
 // ------------------------------------------------------------------------------------------------
@@ -2144,6 +2425,63 @@ extern "C" int d3h_composite_antialias_bwd(int nsrc, const float* const* src, fl
     const int kt = d3h_ktime_begin(D3H_KT_AA_BWD, (long long)n * a.C, s);
     hipLaunchKernelGGL(aa_composite_bwd_kernel, dim3(d3h_cdiv(n, AA_WG_PIX)), dim3(256), (size_t)256 * (a.C + maxch) * sizeof(float), s, a, rast, pos,
                        pos_bstride, tri, flags, nf, nb, H, W, g_out, d_pos);
+    d3h_ktime_end(kt, s);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// One step of layered compositing (depth peeling): out [nb][H][W][C] = antialias(lerp(under, [src_k, 1], covered * alpha) per source k, rast,
+// pos, tri), C = sum(nch + 1) (kind 3: 1, lerp(under, 1, covered * src), alpha does not enter).  Sources as d3h_composite_antialias_fwd
+// (host arrays; kind 0..3, where 0..2 are one case here: the background is what the caller wrote into `under` [nb][H][W][C]); alpha
+// [nb][H][W] or NULL = 1; rast the layer's raster, flags from d3h_antialias_flags.  The lerp is exact at weight 0 and 1.  `out` must not
+// alias `under`.  C is limited to 64 (the rows of a 256-pixel tile in 64 KB of LDS).
+extern "C" int d3h_layer_composite_antialias_fwd(int nsrc, const float* const* src, const int* stride, const int* nch, const int* kind,
+                                                 const float* alpha, const float* under, const float* rast, const float* pos, int pos_bstride,
+                                                 const int* tri, int nf, const unsigned char* flags, int nb, int H, int W, float* out, void* stream) {
+    CompArgs a;
+    int rc = comp_args(a, nsrc, src, nullptr, stride, nch, kind, nullptr, nullptr, false);
+    if (rc != D3H_OK || !src || !under || !rast || !out || out == under || nb < 0 || H <= 0 || W <= 0 || nf < 0 || (nf > 0 && (!pos || !tri || !flags)))
+        return D3H_ERR_ARG;
+    for (int k = 0; k < nsrc; ++k) if (!src[k]) return D3H_ERR_ARG;
+    const size_t lds = (size_t)256 * a.C * sizeof(float);
+    if (lds > 65536) return D3H_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    size_t n = (size_t)nb * H * W;
+    if (n == 0) return D3H_OK;
+    const int kt = d3h_ktime_begin(D3H_KT_AA_FWD, (long long)n * a.C, s);
+    hipLaunchKernelGGL(layer_composite_fwd_kernel, dim3(d3h_cdiv(n, AA_WG_PIX)), dim3(256), lds, s, a, alpha, under, rast, pos, pos_bstride, tri, flags,
+                       nf, nb, H, W, out);
+    d3h_ktime_end(kt, s);
+    D3H_LAUNCH_CHECK();
+    return D3H_OK;
+}
+
+// Backward of d3h_layer_composite_antialias_fwd (same description; g_out [nb][H][W][C]).  dsrc[k] [nb][H][W][dch[k]] (dch NULL = nch; wider:
+// trailing channels zero-filled), d_alpha [nb][H][W], d_under [nb][H][W][C]: each overwritten completely, or NULL = not wanted and not
+// written (dsrc itself may be NULL); d_pos accumulated -- the caller zero-fills -- or NULL.  d(src) = g w, d(under) = g (1 - w), d(alpha) =
+// covered * sum over the sources of kind 0..2 and their channels of g (end - under), g the gradient of the pre-antialias row; no atomics
+// but those of d_pos.  C + max(dch) is limited to 64.
+extern "C" int d3h_layer_composite_antialias_bwd(int nsrc, const float* const* src, float* const* dsrc, const int* dch, const int* stride, const int* nch,
+                                                 const int* kind, const float* alpha, const float* under, const float* rast, const float* pos,
+                                                 int pos_bstride, const int* tri, int nf, const unsigned char* flags, int nb, int H, int W,
+                                                 const float* g_out, float* d_alpha, float* d_under, float* d_pos, void* stream) {
+    CompArgs a;
+    int rc = comp_args(a, nsrc, src, dsrc, stride, nch, kind, nullptr, nullptr, false, dch);
+    if (rc != D3H_OK || !src || !under || !rast || !g_out || d_under == g_out || nb < 0 || H <= 0 || W <= 0 || nf < 0 || (nf > 0 && (!pos || !tri || !flags)))
+        return D3H_ERR_ARG;
+    int maxch = 1;
+    for (int k = 0; k < nsrc; ++k) {
+        if (!src[k]) return D3H_ERR_ARG;
+        if (a.s[k].d && a.s[k].dch > maxch) maxch = a.s[k].dch;
+    }
+    const size_t lds = (size_t)256 * (a.C + maxch) * sizeof(float);
+    if (lds > 65536) return D3H_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    size_t n = (size_t)nb * H * W;
+    if (n == 0) return D3H_OK;
+    const int kt = d3h_ktime_begin(D3H_KT_AA_BWD, (long long)n * a.C, s);
+    hipLaunchKernelGGL(layer_composite_bwd_kernel, dim3(d3h_cdiv(n, AA_WG_PIX)), dim3(256), lds, s, a, alpha, under, rast, pos, pos_bstride, tri, flags,
+                       nf, nb, H, W, g_out, d_alpha, d_under, d_pos);
     d3h_ktime_end(kt, s);
     D3H_LAUNCH_CHECK();
     return D3H_OK;

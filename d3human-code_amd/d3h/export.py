@@ -16,10 +16,13 @@ from . import uvatlas as _U
 
 
 @torch.no_grad()
-def textured_mesh(mesh, material, texture_res, kd_min, kd_max, ks_min, ks_max, nrm_min, nrm_max):
+def textured_mesh(mesh, material, texture_res, kd_min, kd_max, ks_min, ks_max, nrm_min, nrm_max, transparency=False, alpha_init=1.0):
     """mesh: render.mesh.Mesh (v_pos [V,3], or [B,V,3] posed frames of which the first is baked); material: dict with 'kd_ks', an MLPTexture3D
     of 6 channels; texture_res: (H, W) or one int.  -> Mesh(v_tex, t_tex_idx, base=mesh) whose material is `material` without 'kd_ks' and with
-    'kd', 'ks', 'normal' as trainable Texture2D ([1,H,W,3] each) clamped to the given ranges and 'filter_mode': 'linear' (module docstring); texels no triangle owns hold the mean of the owned ones."""
+    'kd', 'ks', 'normal' as trainable Texture2D ([1,H,W,3] each) clamped to the given ranges and 'filter_mode': 'linear' (module docstring); texels no triangle owns hold the mean of the owned ones.
+    transparency (FLAGS.transparency of the reference, train.py:233): 'kd' is [1,H,W,4], the fourth channel the opacity render_mesh blends peeled
+    layers with under FLAGS.transparency -- alpha_init everywhere (a number), or uniform random numbers in [0, 1) for alpha_init='rand' (the
+    reference's rand_like); kd_min / kd_max of three entries get the opacity's bounds 0 and 1 appended, four entries are taken as given."""
     v_pos = mesh.v_pos[0] if mesh.v_pos.dim() == 3 else mesh.v_pos
     atlas = _U.make_atlas(v_pos, mesh.t_pos_idx, texture_res)
     pos, owned, _, _ = _U.bake_positions(atlas, v_pos, mesh.t_pos_idx)
@@ -34,7 +37,19 @@ def textured_mesh(mesh, material, texture_res, kd_min, kd_max, ks_min, ks_max, n
     out = _mesh.Mesh(v_tex=atlas.uvs, t_tex_idx=atlas.t_tex_idx, base=mesh)
     out.material = {k: v for k, v in material.items() if k != 'kd_ks'}
     out.material['filter_mode'] = 'linear'
-    out.material.update({'kd': _texture.Texture2D(leaf(tex[..., 0:3]), min_max=rng(kd_min, kd_max)),
+    kd = tex[..., 0:3]
+    if transparency:
+        if isinstance(alpha_init, str):
+            if alpha_init != 'rand':
+                raise ValueError(f"textured_mesh: alpha_init must be a number or 'rand', not {alpha_init!r}")
+            alpha = torch.rand_like(kd[..., 0:1])
+        else:
+            alpha = torch.full_like(kd[..., 0:1], float(alpha_init))
+        kd = torch.cat((kd, alpha), dim=-1)
+        kd_min, kd_max = rng(kd_min, kd_max)
+        if kd_min.numel() == 3:
+            kd_min, kd_max = torch.cat((kd_min, kd_min.new_zeros(1))), torch.cat((kd_max, kd_max.new_ones(1)))
+    out.material.update({'kd': _texture.Texture2D(leaf(kd), min_max=rng(kd_min, kd_max)),
                          'ks': _texture.Texture2D(leaf(tex[..., 3:6]), min_max=rng(ks_min, ks_max)),
                          'normal': _texture.Texture2D(leaf(normal), min_max=rng(nrm_min, nrm_max))})
     return out

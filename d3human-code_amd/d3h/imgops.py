@@ -375,6 +375,78 @@ def composite_antialias_grad(rast, sources, pos, tri):
     return _CompositeAntialiasFn.apply(rast, pos, tri, [s[1] for s in sources], [s[2] for s in sources], use, *srcs)
 
 
+# ---- one step of layered compositing (depth peeling) ------------------------------------------------------------------------------------------
+LAYER_MAX_CHANNELS = 64          # csrc/raster.hip: the rows of a 256-pixel tile in 64 KB of LDS (forward C, backward C + the widest source gradient)
+
+
+class _LayerCompositeAntialiasFn(torch.autograd.Function):
+    """csrc/raster.hip: layer_composite_fwd_kernel / layer_composite_bwd_kernel, one launch each way; the blended, pre-antialias image is never
+    stored.  Only the gradients somebody asks for are allocated and written."""
+
+    @staticmethod
+    def forward(ctx, rast, pos, tri, kinds, flags, alpha, under, *srcs):
+        from . import raster as _R
+        B, H, W = rast.shape[:3]
+        n = len(srcs)
+        views = [_pix_view(s) for s in srcs]
+        nch = [int(v[0].shape[-1]) for v in views]
+        C = sum(1 if k == COMP_ALPHA else c + 1 for k, c in zip(kinds, nch))
+        rc, pos_c, tri_c = rast.contiguous(), pos.contiguous().float(), tri.contiguous()
+        under_c = under.contiguous().float()
+        if tuple(under_c.shape) != (B, H, W, C):
+            raise ValueError(f'layer_composite_antialias: under must be [{B}, {H}, {W}, {C}], not {tuple(under.shape)}')
+        widest = max([c for k, c in enumerate(nch) if ctx.needs_input_grad[7 + k]], default=0)
+        if C > LAYER_MAX_CHANNELS or (widest and C + widest > LAYER_MAX_CHANNELS):
+            raise ValueError(f'layer_composite_antialias: {C} channels' + (f' + a source gradient of {widest}' if widest else '') +
+                             f' exceed the {LAYER_MAX_CHANNELS} a tile has room for; composite fewer buffers per call')
+        alpha_c = None if alpha is None else alpha.float().expand(B, H, W, 1).contiguous()
+        if flags is None:
+            flags = _R._edge_flags(pos_c, tri_c, B, H, W)
+        out = torch.empty(B, H, W, C, dtype=torch.float32, device=rast.device)
+        I = ctypes.c_int * n
+        L.call('layer_composite_antialias_fwd', n, L.ptr_array([v[0] for v in views], strided=True), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
+               alpha_c, under_c, rc, pos_c, _R._bstride(pos_c), tri_c, tri_c.shape[0], flags, B, H, W, out)
+        ctx.save_for_backward(rc, pos_c, tri_c, flags, alpha_c, under_c, *[v[0] for v in views])
+        ctx.meta = (kinds, nch, [s.shape for s in srcs], [int(v[1]) for v in views], None if alpha is None else alpha.shape, under.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import raster as _R
+        kinds, nch, shapes, strides, ashape, ushape = ctx.meta
+        n = len(nch)
+        rc, pos_c, tri_c, flags, alpha_c, under_c = ctx.saved_tensors[:6]
+        views = ctx.saved_tensors[6:]
+        B, H, W = rc.shape[:3]
+        g = g.contiguous().float()
+        new = lambda c: torch.empty(B, H, W, c, dtype=torch.float32, device=g.device)
+        ds = [new(c) if ctx.needs_input_grad[7 + k] else None for k, c in enumerate(nch)]
+        d_alpha = new(1) if (alpha_c is not None and ctx.needs_input_grad[5]) else None
+        d_under = torch.empty_like(under_c) if ctx.needs_input_grad[6] else None
+        d_pos = L.zeros_like(pos_c) if ctx.needs_input_grad[1] else None
+        I = ctypes.c_int * n
+        L.call('layer_composite_antialias_bwd', n, L.ptr_array(views, strided=True), L.ptr_array(ds), I(*nch), I(*strides), I(*nch), I(*kinds),
+               alpha_c, under_c, rc, pos_c, _R._bstride(pos_c), tri_c, tri_c.shape[0], flags, B, H, W, g, d_alpha, d_under, d_pos)
+        red = lambda d, shp: None if d is None else d.sum_to_size(shp)
+        return (None, d_pos, None, None, None, red(d_alpha, ashape), red(d_under, ushape)) + tuple(red(d, shp) for d, shp in zip(ds, shapes))
+
+
+def layer_composite_antialias(rast, sources, alpha, under, pos, tri, flags=None):
+    """One step of layered compositing, back to front (render/render.py's docstring states the whole contract): layer `rast` laid over `under`
+    and antialiased along its own silhouettes,
+        out = antialias(lerp(under, [values_k, 1], w) for every source k, rast, pos, tri),   w = (rast[..., 3] > 0) * alpha.
+    sources: list of (values [B,H,W,c] (a strided slice is fine), kind[, ...]) as for composite(); kinds COMP_ZERO / COMP_IMAGE / COMP_CONST20 are
+    one case here (c + 1 channels, the last the layer's opacity; their backgrounds are what the caller put into the deepest `under`), COMP_ALPHA
+    (c = 1) is lerp(under, 1, coverage * values) in one channel, which `alpha` does not enter.  alpha: [B,H,W,1] or None (= 1); under:
+    [B,H,W,sum of the widths], not modified.  The lerp is torch.lerp's two-branch form: exact at w = 0 (under) and w = 1 (the source), so a
+    layer that covers nothing returns `under` bit for bit.  Differentiable in every source, alpha, under and pos (d_pos by float atomics, everything
+    else gathered); under torch.no_grad() only the forward kernel runs.  flags: d3h.raster._edge_flags(pos, tri, ...), which depend on (pos, tri)
+    only -- a caller that composites several layers passes the same ones to every step.  At most LAYER_MAX_CHANNELS channels."""
+    B, H, W = rast.shape[:3]
+    srcs = [s[0].expand(B, H, W, s[0].shape[-1]) for s in sources]
+    return _LayerCompositeAntialiasFn.apply(rast, pos, tri, [int(s[1]) for s in sources], flags, alpha, under, *srcs)
+
+
 # ---- fused per-pixel loss stack of tick_init / tick_split -------------------------------------------------------------------
 SSIM_OCC = os.environ.get('D3H_SSIM_OCC', '1') != '0'
 PIXEL_LOSS_KEYS = ('mask_mse', 'img', 'msdf_pos_l1', 'msdf_neg_l1', 'normal_mse', 'normal_cos', 'kd_grad', 'ks_grad', 'normal_grad', 'ssim')

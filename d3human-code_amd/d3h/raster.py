@@ -41,7 +41,8 @@ Antialias options:
   - pos_gradient_boost: d_pos is multiplied by it; the colour gradient is unchanged.
   - topology_hash = antialias_construct_topology_hash(tri): the edge hash built once in buffers of its own and reused; results are
     bit-identical to calling without it.  A hash built for another triangle count raises ValueError.
-  - Not covered: OpenGL-only options of nvdiffrast; layered compositing of peeled layers in render/render.py (it asserts num_layers == 1).
+  - Not covered: OpenGL-only options of nvdiffrast.  Peeled layers are shaded and blended by render/render.py:render_mesh(num_layers=...), one
+    d3h.imgops.layer_composite_antialias step per layer (csrc/raster.hip: layer_composite_*_kernel).
 """
 import os
 import torch

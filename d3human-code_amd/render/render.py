@@ -21,8 +21,27 @@ outputs.  'kd_grad' / 'ks_grad' are SCREEN-SPACE there, built like normal_grad: 
 bilinear / clamp lookup of the image at the jittered pixel grid -- the reference has no 2-D rule (its jitter is a 3-D position offset into the MLP),
 and a jitter in uv space would leave the triangle's cell of the atlas.  The lookups are one fused pass (d3h.texmat) when the mode is 'linear', the
 raster and v_tex need no gradient and shading runs at the visibility resolution; else interpolate + texture, which gives the same values.
-D3H_TEXMAT_FUSED=0 / 1 forces the composed / fused route where both apply (default: profiles/texmat_probe.md).  A 4-channel kd (transparency) is not
-built.
+D3H_TEXMAT_FUSED=0 / 1 forces the composed / fused route where both apply (default: profiles/texmat_probe.md).
+
+Layers and transparency (FLAGS.layers, FLAGS.transparency of the reference: train.py:449,1578,233; render.py:91-92,179-204,375-382).  The contract:
+let L = num_layers >= 1, peeled front to back as rast_0 .. rast_{L-1}.  Layer l is shaded exactly as the single layer is: its own G-buffer pass, its
+own material lookup and its own shade(); with spp > 1 or msaa its own scaling.  Its opacity A_l [B,H,W,1] is the fourth channel of the looked-up kd
+(which the Texture2D has clamped); everything that read kd reads kd[..., :3].  A material without that channel, and any MLP material, has A_l = 1.
+For every output buffer k with n_k value channels
+    acc = background_k               # n_k + 1 channels: 'shaded' = [background rgb, 0]; 'depth' = 20 in all n_k + 1 channels; others 0
+    for l = L-1 .. 0:                # back to front
+        w   = (rast_l[..., 3] > 0) * A_l
+        acc = lerp(acc, [value_{k,l}, 1], w)
+        acc = antialias(acc, rast_l, v_pos_clip, tri)
+    out_k = avg_pool(acc, spp) if spp > 1 else acc
+'msdf_image' keeps its rule: one channel, w = coverage_l * msdf_l, end value 1 (A_l does not enter).  'visible_triangles', '_seen_faces' and '_rast'
+come from layer 0.  The lerp is torch.lerp's two-branch form, exact at w = 0 (returns acc) and w = 1 (returns the source): a layer that covers
+nothing is the identity, bit for bit.  Gates: the opacity is read only when getattr(FLAGS, 'transparency', False) is true -- without the flag a
+4-channel kd raises NotImplementedError, as before; every call with num_layers == 1 and no opacity channel runs the single-layer code unchanged;
+num_layers > 1 needs no flag (opaque layers are valid); num_layers < 1 raises ValueError; FLAGS.lit_shading with num_layers > 1 raises
+NotImplementedError (shadow rays per layer are not built).  One blend step is d3h.imgops.layer_composite_antialias (one kernel each way, under
+torch.no_grad() the forward one only) or, with D3H_LAYER_FUSED=0, torch.lerp + dr.antialias on the channel-concatenated image (default:
+profiles/layers_probe.md).
 
 `mesh.v_pos` may be [P,3] (the reference) or [B,P,3] (one posed mesh per frame of the batch: the build's N-frame extension,
 SURVEY F5).  spp > 1 is not part of the hot path (FLAGS.spp = 1) and raises.
@@ -47,6 +66,7 @@ LIT_BSDFS = ('pbr', 'diffuse', 'white')
 BSDFS = ('kd', 'ks', 'normal', 'tangent') + LIT_BSDFS
 PERTURBED_BUFFERS = ('perturbed_nrm', 'perturbed_nrm_grad')   # render.py:202-204: present only when a normal map perturbs the shading normal
 TEXMAT_FUSED_DEFAULT = True                                # profiles/texmat_probe.md
+LAYER_FUSED_DEFAULT = True                                 # profiles/layers_probe.md
 rnd_seed = 0                                               # render.py:128-132: the sampler's seed, one step per lit shade
 
 
@@ -173,6 +193,11 @@ def _texmat_fused():
     return TEXMAT_FUSED_DEFAULT if env is None else env != '0'
 
 
+def _layer_fused():
+    env = os.environ.get('D3H_LAYER_FUSED')
+    return LAYER_FUSED_DEFAULT if env is None else env != '0'
+
+
 def _material_lookups(mesh, rast, db, names, same_res, mask):
     """{name: [B,H,W,C]} of the material's maps `names` at the pixels' texel coordinates (module docstring), zero at uncovered pixels on either
     route (the composed lookups read texel (0, 0) there: masked, so that the screen-space taps next to the silhouette see the same image)"""
@@ -234,13 +259,16 @@ def shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, g
     fused_dead = tex2d is None and (not fused) and ({'kd_grad', 'ks_grad'} <= want) and grad_on and not any(is_live(k) for k in smooth)
     if tex2d is not None:
         # ---- 2-D material: the maps at the texel coordinate; the smoothness terms in screen space (module docstring)
-        names = [k for k, users in (('kd', {'shaded', 'kd', 'kd_grad'}), ('ks', {'ks', 'ks_grad'})) if want & users]
+        names = [k for k, users in (('kd', {'shaded', 'kd', 'kd_grad'}), ('ks', {'ks', 'ks_grad'})) if want & users or (k == 'kd' and tex2d.get('alpha'))]
         nrm_users = {'normal', 'perturbed_nrm', 'perturbed_nrm_grad'}
         if tex2d['perturb'] and want & nrm_users:
             names.append('normal')
-        with on(*tex_users, *nrm_users):
+        # (the opacity weighs EVERY buffer of the layer: with it the lookup is differentiable whenever any buffer is live)
+        with (torch.set_grad_enabled(grad_on and (live is None or bool(live))) if tex2d.get('alpha') else on(*tex_users, *nrm_users)):
             vals = tex2d['lookup'](names)
         kd, ks, perturbed_nrm = vals.get('kd'), vals.get('ks'), vals.get('normal')
+        if tex2d.get('alpha'):                       # FLAGS.transparency (render.py:91-92): kd = (colour, the layer's opacity)
+            out['_alpha'], kd = kd[..., 3:4], kd[..., 0:3]
         ks = ks[..., 0:3] if ks is not None else None
         if want & {'kd_grad', 'ks_grad', 'perturbed_nrm_grad'}:
             jitter = (util.pixel_grid(W, H, device=dev)[None, ...] + offset).contiguous()
@@ -351,7 +379,12 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     `_grad_buffers` (extension, tick_*): the buffers whose gradient somebody will ask for; the others are produced under
     torch.no_grad() and composited / antialiased in a pass of their own, so the backward of a tick that renders all 12 buffers costs
     what the backward of the three to seven it reads costs.  None = every buffer is differentiable, as in the reference."""
-    assert num_layers == 1
+    num_layers = int(num_layers)
+    if num_layers < 1:
+        raise ValueError(f'render_mesh: num_layers must be at least 1, got {num_layers}')
+    if num_layers > 1 and getattr(FLAGS, 'lit_shading', False):
+        raise NotImplementedError('render_mesh: FLAGS.lit_shading with num_layers > 1 (shadow rays per peeled layer) is not built')
+    transparency = bool(getattr(FLAGS, 'transparency', False))
     spp = int(spp)
     H, W = int(resolution[0]), int(resolution[1])
     Hf, Wf = H * spp, W * spp                     # visibility resolution (render.py:239); == (H, W) in every configuration of train.py (spp = 1)
@@ -369,7 +402,7 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     if tex2d:
         if mesh.v_tex is None or mesh.t_tex_idx is None:
             raise ValueError("render_mesh: a material with 'kd' / 'ks' texture maps needs mesh.v_tex and mesh.t_tex_idx")
-        if mesh.material['kd'].getChannels() == 4:
+        if mesh.material['kd'].getChannels() == 4 and not transparency:
             raise NotImplementedError('render_mesh: a 4-channel kd (transparency, FLAGS.transparency of the reference) is not built')
         perturb = bool(use_uv and finetune_normal and isinstance(mesh.material.get('normal'), _Texture2D)
                        and not mesh.material.get('no_perturbed_nrm', False) and mesh.v_tng is not None)
@@ -377,6 +410,7 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
             want |= set(PERTURBED_BUFFERS)
     if not perturb:
         want -= set(PERTURBED_BUFFERS)
+    has_alpha = bool(tex2d and transparency and mesh.material['kd'].getChannels() == 4)
     live = None if (_grad_buffers is None or not grad_on) else (want & set(_grad_buffers))
     # ---- FLAGS.lit_shading: the colour follows the bsdf (render.py:117-176).  `want` grows by what the lit colour is made of, so that a caller that
     # reads only 'shaded' still gets positions, shading normal, kd / ks and the denoiser's (z, |dz|); `want_out` / `live_out` stay what was asked for
@@ -410,12 +444,9 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     # grad_db=False: db feeds the no-grad z-gradient pass only, so its (spp > 1) rescale below records no autograd node
     with dr.DepthPeeler(ctx, v_pos_clip, tri, [Hf, Wf], grad_db=False) as peeler:
         mip_uv = tex2d and mesh.material.get('filter_mode', 'linear-mipmap-linear').startswith('linear-mipmap')     # the texel footprint
-        rast_full, db_full = peeler.rasterize_next_layer(want_db='z_grad' in want or mip_uv)
-    rast, db = rast_full, db_full
-    if spp > 1 and msaa:                          # shade at the framebuffer resolution (render.py:241-245): nearest sample of the raster
-        rast = util.scale_img_nhwc(rast_full, [H, W], mag='nearest', min='nearest')
-        db = util.scale_img_nhwc(db_full, [H, W], mag='nearest', min='nearest') * spp if db_full is not None else None
-    elif spp > 1:
+        peeled = [peeler.rasterize_next_layer(want_db='z_grad' in want or mip_uv) for _ in range(num_layers)]      # front to back
+    rast_full = peeled[0][0]
+    if spp > 1 and not msaa:
         H, W = Hf, Wf                             # no msaa: everything at the visibility resolution, averaged at the end
 
     F = tri.shape[0]
@@ -444,47 +475,61 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
     nb_attr = max(t.shape[0] for _, t in srcs)
     packed = torch.cat([t.expand(nb_attr, -1, -1) for _, t in srcs], dim=-1) if len(srcs) > 1 else srcs[0][1]
     fn = _I.face_normals(v_pos, tri) if want & {'geometric_normal', 'normal'} else None      # [B,F,3], one launch
-    # (the raster's only differentiable consumer at the shading resolution == visibility resolution is this pass -- antialias and composite take
-    # it as a constant, the z / depth pass runs under no_grad --: its backward is folded into the G-buffer's, d3h.raster.gbuffer)
-    fold = (H, W) == (Hf, Wf) and os.environ.get('D3H_FUSED_GBUFFER_RASTER_BWD', '1') != '0'
-    groups, gb_geometric_normal, cover = _R.gbuffer(packed, [t.shape[-1] for _, t in srcs], rast, tri, face_attr=fn, want_mask=True,
-                                                    raster_pos=v_pos_clip if fold else None)
-    gb = {k: g for (k, _), g in zip(srcs, groups)}
-    gb_pos, gb_pos_original, gb_normal, gb_msdf = gb.get('pos'), gb.get('orig'), gb.get('nrm'), gb.get('msdf')
-    if need_nrm and own_nrm_idx:
-        gb_normal, _ = interpolate(_batched(mesh.v_nrm), rast, mesh.t_nrm_idx.int())                  # render.py:272
-
-    gb_tangent = None
-    if perturb and 'normal' in want:
-        gb_tangent, _ = interpolate(_batched(mesh.v_tng), rast, mesh.t_tng_idx.int())                # render.py:273
-    elif 'normal' in want:
-        with torch.no_grad():                                                    # render.py:284-287 (use_uv == False branch)
-            noise = torch.randn_like(gb_normal) if _rng_draws is None else _rng_draws['noise'].to(dev)
-            noise = noise / noise.norm(dim=-1, keepdim=True)
-        gb_tangent = torch.cross(noise, gb_normal, dim=-1)
-
-    # forward-only buffers in one fused pass: z / z-gradient (torch.no_grad in the reference, render.py:291-299) and, when nobody
-    # differentiates them (the reference does only under FLAGS.use_depth), depth / inverse depth (render.py:197-199)
-    aux = (None, None, None)
-    if need_aux:
-        aux = _R.aux_buffers(v_pos_clip, rast, db, tri, gb_pos, view_pos, want_z='z_grad' in want, want_depth=no_grad_of('depth'),
-                             want_invdepth=no_grad_of('invdepth'))
-
     if lit is not None and lit[0] in LIT_BSDFS:
         lit = (lit[0], lit[1], _frame_contexts(optix_ctx, B), lit[3], lit[4])
-    layer = shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, gb_normal, gb_tangent, view_pos, mesh.material,
-                  want, finetune_normal, mask=cover, rng_draws=_rng_draws, live=live, skip_uncovered=(H, W) == (Hf, Wf), lit=lit,
-                  tex2d={'lookup': lambda names: _material_lookups(mesh, rast, db, names, (H, W) == (Hf, Wf), cover), 'perturb': perturb} if tex2d else None)
+
+    def shade_layer(rast_full, db_full):
+        """one peeled layer, shaded exactly as the single layer of the reference: -> ({buffer: values at the visibility resolution}, the texture MLP's
+        whole output when 'shaded' is its channel prefix, the layer's opacity [B,Hf,Wf,1] or None = 1)"""
+        rast, db = rast_full, db_full
+        if spp > 1 and msaa:                          # shade at the framebuffer resolution (render.py:241-245): nearest sample of the raster
+            rast = util.scale_img_nhwc(rast_full, [H, W], mag='nearest', min='nearest')
+            db = util.scale_img_nhwc(db_full, [H, W], mag='nearest', min='nearest') * spp if db_full is not None else None
+        # (the raster's only differentiable consumer at the shading resolution == visibility resolution is this pass -- antialias and composite take
+        # it as a constant, the z / depth pass runs under no_grad --: its backward is folded into the G-buffer's, d3h.raster.gbuffer)
+        fold = (H, W) == (Hf, Wf) and os.environ.get('D3H_FUSED_GBUFFER_RASTER_BWD', '1') != '0'
+        groups, gb_geometric_normal, cover = _R.gbuffer(packed, [t.shape[-1] for _, t in srcs], rast, tri, face_attr=fn, want_mask=True,
+                                                        raster_pos=v_pos_clip if fold else None)
+        gb = {k: g for (k, _), g in zip(srcs, groups)}
+        gb_pos, gb_pos_original, gb_normal, gb_msdf = gb.get('pos'), gb.get('orig'), gb.get('nrm'), gb.get('msdf')
+        if need_nrm and own_nrm_idx:
+            gb_normal, _ = interpolate(_batched(mesh.v_nrm), rast, mesh.t_nrm_idx.int())                  # render.py:272
+
+        gb_tangent = None
+        if perturb and 'normal' in want:
+            gb_tangent, _ = interpolate(_batched(mesh.v_tng), rast, mesh.t_tng_idx.int())                # render.py:273
+        elif 'normal' in want:
+            with torch.no_grad():                                                    # render.py:284-287 (use_uv == False branch)
+                noise = torch.randn_like(gb_normal) if _rng_draws is None else _rng_draws['noise'].to(dev)
+                noise = noise / noise.norm(dim=-1, keepdim=True)
+            gb_tangent = torch.cross(noise, gb_normal, dim=-1)
+
+        # forward-only buffers in one fused pass: z / z-gradient (torch.no_grad in the reference, render.py:291-299) and, when nobody
+        # differentiates them (the reference does only under FLAGS.use_depth), depth / inverse depth (render.py:197-199)
+        aux = (None, None, None)
+        if need_aux:
+            aux = _R.aux_buffers(v_pos_clip, rast, db, tri, gb_pos, view_pos, want_z='z_grad' in want, want_depth=no_grad_of('depth'),
+                                 want_invdepth=no_grad_of('invdepth'))
+
+        layer = shade(FLAGS, idx, rast, aux, gb_pos, gb_pos_original, gb_geometric_normal, gb_normal, gb_tangent, view_pos, mesh.material,
+                      want, finetune_normal, mask=cover, rng_draws=_rng_draws, live=live, skip_uncovered=(H, W) == (Hf, Wf), lit=lit,
+                      tex2d={'lookup': lambda names: _material_lookups(mesh, rast, db, names, (H, W) == (Hf, Wf), cover), 'perturb': perturb,
+                             'alpha': has_alpha} if tex2d else None)
+        if lit is not None:
+            layer = {k: t for k, t in layer.items() if k in want_out or k == '_alpha'}      # what the lit colour was made of is not an output unless asked for
+        shaded_of = layer.pop('_shaded_of', None)
+        if (H, W) != (Hf, Wf):
+            shaded_of = None
+        if has_msdf:
+            layer['msdf_image'] = gb_msdf
+        if (H, W) != (Hf, Wf):                        # back up to the visibility resolution (render.py:334-336)
+            layer = {k: (util.scale_img_nhwc(t, [Hf, Wf], mag='nearest', min='nearest') if t is not None else None) for k, t in layer.items()}
+        return layer, shaded_of, layer.pop('_alpha', None)
+
+    layers = [shade_layer(r, d) for r, d in peeled]
+    layer, shaded_of, _ = layers[0]
     if lit is not None:
-        layer = {k: t for k, t in layer.items() if k in want_out}              # what the lit colour was made of is not an output unless asked for
         want, live = want_out, live_out
-    shaded_of = layer.pop('_shaded_of', None)
-    if (H, W) != (Hf, Wf):
-        shaded_of = None
-    if has_msdf:
-        layer['msdf_image'] = gb_msdf
-    if (H, W) != (Hf, Wf):                        # back up to the visibility resolution (render.py:334-336)
-        layer = {k: (util.scale_img_nhwc(t, [Hf, Wf], mag='nearest', min='nearest') if t is not None else None) for k, t in layer.items()}
 
     # ---- composite against each buffer's background (one pass), then ONE antialias pass over all channels (render.py:375-382,430-449)
     if background is None:
@@ -517,6 +562,43 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
             img = dr.antialias(_I.composite(rast_full, sources), rast_full, v_pos_clip, tri)
         return (util.avg_pool_nhwc(img, spp) if spp > 1 else img), widths                              # render.py:449
 
+    layer_flags = []
+
+    def edge_flags():
+        """the silhouette-edge bits depend on (pos, tri) only: once per call, not per layer or group of buffers"""
+        if not layer_flags:
+            layer_flags.append(_R._edge_flags(v_pos_clip.detach().contiguous().float(), tri.contiguous(), B, Hf, Wf))
+        return layer_flags[0]
+
+    def compose_layers(keys):
+        """the module docstring's loop over the peeled layers, back to front, on the channel-concatenated image of the buffers `keys`"""
+        widths = [1 if k == 'msdf_image' else layer[k].shape[-1] + 1 for k in keys]
+        kind = {'shaded': _I.COMP_IMAGE, 'depth': _I.COMP_CONST20, 'msdf_image': _I.COMP_ALPHA}
+        # what lies behind the deepest layer: every buffer's background, written once (DESIGN 7)
+        acc = torch.zeros(B, Hf, Wf, sum(widths), dtype=torch.float32, device=dev)
+        c0 = 0
+        for k, n in zip(keys, widths):
+            if k == 'shaded':
+                acc[..., c0:c0 + 3] = background
+            elif k == 'depth':
+                acc[..., c0:c0 + n] = 20.0
+            c0 += n
+        fused = _layer_fused()
+        flags = edge_flags() if fused else None
+        for (lay, _, a), (r, _) in reversed(list(zip(layers, peeled))):
+            if fused:
+                acc = _I.layer_composite_antialias(r, [(lay[k], kind.get(k, _I.COMP_ZERO)) for k in keys], a, acc, v_pos_clip, tri, flags=flags)
+                continue
+            cov = (r[..., 3:4] > 0).float()
+            w = cov if a is None else cov * a
+            one = torch.ones_like(cov)
+            end = torch.cat([one if k == 'msdf_image' else torch.cat((lay[k].expand(B, Hf, Wf, -1), one), dim=-1) for k in keys], dim=-1)
+            if 'msdf_image' in keys:                  # its value IS its weight (render.py:444-449)
+                w = torch.cat([cov * lay[k] if k == 'msdf_image' else w.expand(-1, -1, -1, n) for k, n in zip(keys, widths)], dim=-1)
+            acc = dr.antialias(torch.lerp(acc, end, w), r, v_pos_clip, tri)
+        return (util.avg_pool_nhwc(acc, spp) if spp > 1 else acc), widths
+
+    layered = num_layers > 1 or has_alpha
     all_keys = [k for k in list(ALL_BUFFERS) + ['msdf_image'] + list(LIT_BUFFERS) + list(PERTURBED_BUFFERS) if k in layer]
     live_keys = all_keys if live is None else [k for k in all_keys if k in live]
     dead_keys = [k for k in all_keys if k not in live_keys]
@@ -530,7 +612,7 @@ def render_mesh(FLAGS, idx, ctx, mesh, mesh_original, mtx_in, view_pos, lgt, res
         for first in range(0, len(keys), 12):
             chunk = keys[first:first + 12]
             with torch.set_grad_enabled(grad_on and not no_grad):
-                stacked, widths = compose(chunk)
+                stacked, widths = compose_layers(chunk) if layered else compose(chunk)
             if first == 0:
                 out_buffers[name] = stacked
             c0 = 0
