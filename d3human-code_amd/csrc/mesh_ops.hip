@@ -8,7 +8,7 @@
 // The reference rebuilds a sparse V x V matrix from the edge list on every call (mesh.py:259-263 recomputes the property each
 // time) and runs a sparse mm; the topology is static in this stage, so the host builds a CSR adjacency once and both L V and its
 // transpose are atomic-free gathers.  All three are HBM/latency-bound passes over 10^4-10^5 elements.
-#include "d3h_vec.h"
+#include "d3h_meshdist_dev.h"
 
 namespace {
 
@@ -134,30 +134,7 @@ __global__ void face_centers_kernel(const float* __restrict__ v, const int* __re
 // triangles staged through LDS as (v0, e1, e2): 262 144 queries x 20 908 SMPL-X faces = 5.5e9 pairs, start-up only.
 constexpr int MSDF_TILE = 1024;
 
-__device__ __forceinline__ float tri_dist2(V3 p, V3 a, V3 ab, V3 ac) {
-    V3 ap = p - a;
-    float d1 = dot(ab, ap), d2 = dot(ac, ap);
-    if (d1 <= 0.f && d2 <= 0.f) return dot(ap, ap);                                   // vertex a
-    V3 bp = ap - ab;
-    float d3 = dot(ab, bp), d4 = dot(ac, bp);
-    if (d3 >= 0.f && d4 <= d3) return dot(bp, bp);                                     // vertex b
-    float vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { V3 q = ap - ab * (d1 / (d1 - d3)); return dot(q, q); }      // edge ab
-    V3 cp = ap - ac;
-    float d5 = dot(ab, cp), d6 = dot(ac, cp);
-    if (d6 >= 0.f && d5 <= d6) return dot(cp, cp);                                     // vertex c
-    float vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { V3 q = ap - ac * (d2 / (d2 - d6)); return dot(q, q); }      // edge ac
-    float va = d3 * d6 - d5 * d4;
-    if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {                           // edge bc
-        float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        V3 q = bp - (ac - ab) * w;
-        return dot(q, q);
-    }
-    float denom = 1.0f / (va + vb + vc);                                               // interior
-    V3 q = ap - ab * (vb * denom) - ac * (vc * denom);
-    return dot(q, q);
-}
+// tri_dist2, vos_term, wsdf_angle_f64: d3h_meshdist_dev.h (shared with the BVH queries of bvhdist.hip)
 
 __global__ __launch_bounds__(256) void mesh_sdf_kernel(const float* __restrict__ pts, int np, const float* __restrict__ v, const int* __restrict__ f,
                                                        int nf, float* __restrict__ out) {
@@ -178,11 +155,8 @@ __global__ __launch_bounds__(256) void mesh_sdf_kernel(const float* __restrict__
         for (int t = 0; t < cnt; ++t) {
             V3 a = ld3(tri + 9 * t), ab = ld3(tri + 9 * t + 3), ac = ld3(tri + 9 * t + 6);
             best = fminf(best, tri_dist2(p, a, ab, ac));
-            V3 ra = a - p, rb = ra + ab, rc = ra + ac;
-            float la = sqrtf(dot(ra, ra)), lb = sqrtf(dot(rb, rb)), lc = sqrtf(dot(rc, rc));
-            float det = dot(ra, cross(rb, rc));
-            float den = la * lb * lc + dot(ra, rb) * lc + dot(ra, rc) * lb + dot(rb, rc) * la;
-            wind += 2.0f * atan2f(det, den);
+            const VosTerm s = vos_term(p, a, ab, ac);
+            wind += 2.0f * atan2f(s.det, s.den);
         }
     }
     // winding number 1 inside an outward-wound closed mesh; positive OUTSIDE, negative inside (= -pysdf, the sign hmsdf.py:237 uses)
@@ -196,21 +170,6 @@ __global__ __launch_bounds__(256) void mesh_sdf_kernel(const float* __restrict__
 // mesh_sdf_kernel makes it, so that a closed mesh gives mesh_sdf's bits (a query within rounding of an edge or a vertex of the mesh excepted, where
 // the triangles it lies on are evaluated in float64, see the loop, and mesh_sdf's float32 residue may put the sign of a zero distance either way).  For an open, consistently wound mesh the |w| = 0.5 surface closes the holes.
 // Either output may be NULL.
-// 2 atan2(det, den) of van Oosterom-Strackee for one triangle, in float64 from the float32 vertices
-__device__ float wsdf_angle_f64(V3 p, const float* __restrict__ v, const int* __restrict__ ff) {
-    double r[3][3], l[3];
-    for (int k = 0; k < 3; ++k) {
-        const float* q = v + 3 * (size_t)ff[k];
-        r[k][0] = (double)q[0] - (double)p.x, r[k][1] = (double)q[1] - (double)p.y, r[k][2] = (double)q[2] - (double)p.z;
-        l[k] = sqrt(r[k][0] * r[k][0] + r[k][1] * r[k][1] + r[k][2] * r[k][2]);
-    }
-    const double cx = r[1][1] * r[2][2] - r[1][2] * r[2][1], cy = r[1][2] * r[2][0] - r[1][0] * r[2][2], cz = r[1][0] * r[2][1] - r[1][1] * r[2][0];
-    const double det = r[0][0] * cx + r[0][1] * cy + r[0][2] * cz;
-    const double d01 = r[0][0] * r[1][0] + r[0][1] * r[1][1] + r[0][2] * r[1][2], d02 = r[0][0] * r[2][0] + r[0][1] * r[2][1] + r[0][2] * r[2][2];
-    const double d12 = r[1][0] * r[2][0] + r[1][1] * r[2][1] + r[1][2] * r[2][2];
-    return (float)(2.0 * atan2(det, l[0] * l[1] * l[2] + d01 * l[2] + d02 * l[1] + d12 * l[0]));
-}
-
 __global__ __launch_bounds__(256) void mesh_wsdf_kernel(const float* __restrict__ pts, int np, const float* __restrict__ v, const int* __restrict__ f,
                                                         int nf, float* __restrict__ out_sdf, float* __restrict__ out_w) {
     __shared__ float tri[MSDF_TILE * 9];
@@ -230,17 +189,14 @@ __global__ __launch_bounds__(256) void mesh_wsdf_kernel(const float* __restrict_
         for (int t = 0; t < cnt; ++t) {
             V3 a = ld3(tri + 9 * t), ab = ld3(tri + 9 * t + 3), ac = ld3(tri + 9 * t + 6);
             best = fminf(best, tri_dist2(p, a, ab, ac));
-            V3 ra = a - p, rb = ra + ab, rc = ra + ac;
-            float la = sqrtf(dot(ra, ra)), lb = sqrtf(dot(rb, rb)), lc = sqrtf(dot(rc, rc));
-            float det = dot(ra, cross(rb, rc));
-            float den = la * lb * lc + dot(ra, rb) * lc + dot(ra, rc) * lb + dot(rb, rc) * la;
+            const VosTerm s = vos_term(p, a, ab, ac);
             // A query within rounding of the triangle's plane (a point ON the mesh: a vertex of it, a point of an edge): det, and on an edge den too, are
             // rounding residue in float32, and the residue would decide between 0 and +-half a turn.  That triangle alone is evaluated in float64 from
             // the vertices themselves (the staged edges are already rounded); everything else stays mesh_sdf_kernel's arithmetic.
             // `wind` itself is mesh_sdf_kernel's sum, untouched; `fix` collects what the repaired triangles change.
-            const float ang = 2.0f * atan2f(det, den);
+            const float ang = 2.0f * atan2f(s.det, s.den);
             wind += ang;
-            if (fabsf(det) < 1e-4f * (la * lb * lc)) fix += wsdf_angle_f64(p, v, f + 3 * (size_t)(base + t)) - ang;
+            if (fabsf(s.det) < 1e-4f * s.lll) fix += wsdf_angle_f64(p, v, f + 3 * (size_t)(base + t)) - ang;
         }
     }
     if (i >= np) return;

@@ -160,12 +160,22 @@ def mesh_sdf(points, verts, faces):
     return out
 
 
-def mesh_wsdf(points, verts, faces, want_sdf=True, want_w=True, check=True):
+ACCELS = ('brute', 'bvh')
+
+
+def mesh_wsdf(points, verts, faces, want_sdf=True, want_w=True, check=True, accel='brute', beta=3.0, bvh=None):
     """-> (sdf, w) of points [n,3] against the triangle mesh (verts [V,3], faces [F,3], F > 0), which may be OPEN: w is the generalised winding
     number in turns (solid-angle sum / 4 pi), sdf = (|w| > 0.5 ? -1 : +1) * distance to the nearest triangle.  A triangle whose plane the query lies in
     to within rounding (a query ON the mesh) is evaluated in float64, so that w does not hang on float32 residue there.  On a closed mesh sdf is
     mesh_sdf, bit for bit; on an open, consistently wound one the |w| = 0.5 surface closes the holes.  An output that is not wanted is None.
-    check=False skips the range check of the faces (two read-backs) for a caller that has made it, such as a field queried every round."""
+    check=False skips the range check of the faces (two read-backs) for a caller that has made it, such as a field queried every round.
+    accel='brute' (the default) is the loop over every triangle, one thread per query.  accel='bvh' answers from a d3h.raytrace.Bvh -- `bvh` if one is
+    passed (built over these verts and faces: a field queried every round builds once), a fresh one otherwise: O(log F) per query, the same
+    per-triangle arithmetic, the winding number by the tree with the opening parameter `beta` (raytrace.Bvh.winding; beta=inf the exact sum in tree
+    order).  The distance is the brute-force route's minimum unless the mesh has zero-area triangles, which the tree never returns; w, and with it the
+    sign near |w| = 0.5, carries the approximation's error."""
+    if accel not in ACCELS:
+        raise RuntimeError(f'mesh_wsdf: accel must be one of {ACCELS}, got {accel!r}')
     p = points.detach().contiguous().float()
     v = verts.detach().contiguous().float()
     if p.dim() != 2 or p.shape[1] != 3 or v.dim() != 2 or v.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
@@ -173,6 +183,15 @@ def mesh_wsdf(points, verts, faces, want_sdf=True, want_w=True, check=True):
     f = (faces if faces.dtype == torch.int32 else faces.int()).contiguous()
     if check and f.shape[0] > 0 and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
         raise RuntimeError('mesh_wsdf: a face index outside [0, V)')
+    if accel == 'bvh':
+        from . import raytrace as _rt
+        if bvh is None:
+            bvh = _rt.Bvh(v, f)
+        elif not isinstance(bvh, _rt.Bvh) or bvh.F != f.shape[0]:
+            raise RuntimeError('mesh_wsdf: bvh must be a raytrace.Bvh built over these verts and faces')
+        if not (want_sdf or want_w):
+            return None, None
+        return bvh._wsdf('mesh_wsdf', p, beta, want_sdf, want_w)
     sdf = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if want_sdf else None
     w = torch.empty(p.shape[0], dtype=torch.float32, device=p.device) if want_w else None
     L.call('mesh_wsdf', p, p.shape[0], v, f, f.shape[0], sdf, w)

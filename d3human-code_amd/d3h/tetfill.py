@@ -30,10 +30,10 @@ tets' watertight vertices bit for bit, and no vertex of the input surface is a v
         all outside  empty tensors; all inside: t == tets, v == pos
         slivers      a cut arbitrarily close to a lattice vertex gives an arbitrarily thin child, and sdf == 0 at a vertex gives children of
                      zero volume.  Nothing is snapped.
-    fill_mesh(verts, faces, res=64, scale=1.1) -> (v, t, h)
+    fill_mesh(verts, faces, res=64, scale=1.1, accel='brute') -> (v, t, h)
         the lattice is the cube of d3h.watertight.extract -- centred on the bounding box, side = scale x the longest extent,
         synth.kuhn_grid(res, raw=True), pitch h = side / res -- and the field is meshops.mesh_wsdf: on a closed mesh mesh_sdf's bits; an open,
-        consistently wound garment gets its holes closed at |w| = 0.5
+        consistently wound garment gets its holes closed at |w| = 0.5.  accel='bvh': the field by meshops.mesh_wsdf(accel='bvh'), from a tree
 
 One call of clip launches up to three kernels (an emit without output is skipped) and reads the three sizes and the error word back once,
 between the first and the second.  A bad shape or dtype and a tet index outside [0, N) raise RuntimeError before any launch."""
@@ -86,7 +86,7 @@ def clip(pos, sdf, tets):
     return v, t, n_in
 
 
-def fill_mesh(verts, faces, res=64, scale=1.1):
+def fill_mesh(verts, faces, res=64, scale=1.1, accel='brute'):
     from . import watertight as _wt
     v = verts.detach().contiguous().float()
     if v.dim() != 2 or v.shape[1] != 3 or v.shape[0] == 0 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
@@ -97,6 +97,6 @@ def fill_mesh(verts, faces, res=64, scale=1.1):
         raise RuntimeError('fill_mesh: the mesh has no extent')
     unit, tets = _wt._lattice(res, v.device)                              # [-1, 1]^3
     pos = ((lo + hi) * 0.5 + unit * (side * 0.5)).contiguous()
-    sdf, _ = _mo.mesh_wsdf(pos, v, faces, want_w=False)
+    sdf, _ = _mo.mesh_wsdf(pos, v, faces, want_w=False, accel=accel)
     out_v, out_t, _ = clip(pos, sdf, tets)
     return out_v, out_t, side / int(res)

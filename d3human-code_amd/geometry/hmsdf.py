@@ -192,7 +192,7 @@ class HmSDFTetsGeometry(torch.nn.Module):
             # containment sign, positive outside) from the brute-force GPU kernel d3h_mesh_sdf -- no CPU third party at start-up.
             from d3h import meshops as _MO
             faces = self._template_faces()
-            sdf_gt = _MO.mesh_sdf(self.verts, self.smplx_deform.vs_template[0].detach(), faces).reshape(-1, 1)
+            sdf_gt = self._template_sdf(self.verts, self.smplx_deform.vs_template[0].detach(), faces).reshape(-1, 1)
         else:
             sdf_gt = fn(self.verts).reshape(-1, 1).to(self.device)
         if steps > 0:
@@ -206,6 +206,15 @@ class HmSDFTetsGeometry(torch.nn.Module):
             self.sdf_prefit_loss = float(loss.detach())
         if ckp:
             torch.save(self.sdf_net.state_dict(), ckp)
+
+    def _template_sdf(self, points, template, faces):
+        """signed distance to the template, positive outside: the brute-force d3h_mesh_sdf, or with FLAGS.mesh_sdf_accel = 'bvh' (absent: 'brute')
+        the same distance and sign rule answered from a BVH of the template (d3h.meshops.mesh_wsdf, accel)"""
+        from d3h import meshops as _MO
+        accel = _flag(self.FLAGS, 'mesh_sdf_accel', 'brute')
+        if accel == 'brute':
+            return _MO.mesh_sdf(points, template, faces)
+        return _MO.mesh_wsdf(points.reshape(-1, 3), template, faces, want_w=False, accel=accel)[0]
 
     def _template_faces(self):
         if self.smplx_deform.layer.faces is None:
@@ -225,12 +234,12 @@ class HmSDFTetsGeometry(torch.nn.Module):
         faces = self._template_faces()
         template = self.smplx_deform.vs_template[0].detach().float().contiguous()
         with torch.no_grad():
-            v, t, _ = _TF.fill_mesh(template, faces, res=int(_flag(F_, 'tet_smpl_res', 64)), scale=1.1)
+            v, t, _ = _TF.fill_mesh(template, faces, res=int(_flag(F_, 'tet_smpl_res', 64)), scale=1.1, accel=_flag(F_, 'mesh_sdf_accel', 'brute'))
             if _flag(F_, 'out_dir'):
                 os.makedirs(F_.out_dir, exist_ok=True)
                 np.savez(os.path.join(F_.out_dir, 'smpl_template_tet_{}.npz'.format(self.grid_res)), v=v.cpu().numpy(), f=t.cpu().numpy())
             self.tet_smpl_v, self.tet_smpl_f = v, t
-            self.sdf_tet_gt = _MO.mesh_sdf(v, template, faces).reshape(-1, 1)
+            self.sdf_tet_gt = self._template_sdf(v, template, faces).reshape(-1, 1)
             self.generate_edges_smpl()
             msdf = (torch.rand_like(self.tet_smpl_v[:, 0]) - 0.01).clamp(-1, 1)          # hmsdf.py:247
         self.smpl_msdf = torch.nn.Parameter(msdf.clone().detach(), requires_grad=True)

@@ -9,6 +9,8 @@ The route, step by step (reference lines :613-747), and every deviation:
      refine step alone.  There is no collapse, flip or tangential smoothing, so short edges stay and vertices are never moved.
   2. The garment is never made watertight and never extracted (wt.mlx: screened Poisson at depth 8, then pysdf): GarmentField answers the distance
      queries directly on the open garment, as -mesh_wsdf: distance to the nearest triangle, signed by the generalised winding number (|w| > 0.5 inside).
+     field_accel='bvh' (default 'brute': the loop over every triangle) answers them, and the field of step 5, from a d3h.raytrace.Bvh: the garment's is
+     built once for all push rounds.
   3. One ring of open faces is peeled off the cut SMPL, whose vertices are pushed inward along their normals (deform_body_collision: 0.005 per round
      while less than 0.002 inside, at most 100 rounds).  The reference's sweep is a Jacobi sweep too; its kd-tree query per pushed vertex has no effect
      and is left out.  The device route stops when a round moves nothing (the remaining rounds would move nothing either).
@@ -38,6 +40,7 @@ from d3h import imgops as IO
 from d3h import meshops as MO
 from d3h import meshrefine as MR
 from d3h import meshtopo as MT
+from d3h import raytrace as RT
 from d3h import watertight as WT
 from script.connet_face_head import MergedMesh, _device, om_loadmesh, write_pc
 
@@ -99,15 +102,20 @@ def face_in_bbox(v_indices, f):
 
 class GarmentField:
     """the signed distance to the OPEN garment mesh with pysdf's sign (positive inside): -mesh_wsdf.  Callable on numpy [n,3] -> numpy [n], as a
-    pysdf.SDF is; `device(x)` takes and returns tensors on the device"""
+    pysdf.SDF is; `device(x)` takes and returns tensors on the device.  accel='bvh': the garment does not change between the rounds that query it, so
+    one d3h.raytrace.Bvh is built here and every query is answered from it (meshops.mesh_wsdf, accel)"""
 
-    def __init__(self, v, f):
+    def __init__(self, v, f, accel='brute'):
         self.v, self.f = _t(v, np.float32).reshape(-1, 3), _faces(f).int().contiguous()
         if self.f.shape[0] == 0 or int(self.f.min()) < 0 or int(self.f.max()) >= self.v.shape[0]:      # once: the queries below skip the check
             raise RuntimeError('GarmentField: no faces, or a face index outside [0, V)')
+        if accel not in MO.ACCELS:
+            raise RuntimeError(f'GarmentField: accel must be one of {MO.ACCELS}, got {accel!r}')
+        self.accel = accel
+        self.bvh = RT.Bvh(self.v, self.f) if accel == 'bvh' else None
 
     def device(self, x):
-        return -MO.mesh_wsdf(x, self.v, self.f, want_w=False, check=False)[0]
+        return -MO.mesh_wsdf(x, self.v, self.f, want_w=False, check=False, accel=self.accel, bvh=self.bvh)[0]
 
     def __call__(self, x):
         return self.device(_t(x, np.float32).reshape(-1, 3)).cpu().numpy()
@@ -160,7 +168,7 @@ def process_subdivide(body_path, bbox_npz_path, root, script_root=None, local=Fa
 
 def process_body_msdf_distance_bodyedge(FLAGS, root, body_path, ori_cloth_path, smpl_cloth_path, smpl_path, bbox_npz_path, script_root="checkpoints/script",
                                         local=False, *, target_len=0.01, wt_res=128, relax_iters=32, head_threshold=0.002, head_iterations=3, push_eps=0.005,
-                                        push_margin=0.002, push_rounds=100):
+                                        push_margin=0.002, push_rounds=100, field_accel='brute'):
     for p in (body_path, ori_cloth_path, smpl_cloth_path, smpl_path, bbox_npz_path):
         if not os.path.exists(p):
             raise FileNotFoundError(f'process_body_msdf_distance_bodyedge: {p} does not exist')
@@ -170,7 +178,7 @@ def process_body_msdf_distance_bodyedge(FLAGS, root, body_path, ori_cloth_path, 
     cloth_v, cloth_f = _remesh(*om_loadmesh(ori_cloth_path), target_len)
     cut_v, cut_f = _remesh(*om_loadmesh(smpl_cloth_path), target_len)
     # 2. the garment as a distance oracle
-    garment = GarmentField(cloth_v.cpu().numpy(), cloth_f.cpu().numpy())
+    garment = GarmentField(cloth_v.cpu().numpy(), cloth_f.cpu().numpy(), accel=field_accel)
     # 3. one ring off the cut SMPL, pushed under the garment
     cut_f = MT.peel_open_faces(cut_f, cut_v.shape[0], rounds=1)
     cut_v, cut_f = cut_v.cpu().numpy(), cut_f.cpu().numpy()
@@ -182,7 +190,7 @@ def process_body_msdf_distance_bodyedge(FLAGS, root, body_path, ori_cloth_path, 
     write_pc(os.path.join(root, "body_edge_cut.obj"), v=body_v, f=body_f)
     merged = merge_and_repair_meshes(MergedMesh(deformed_v, cut_f), MergedMesh(body_v, body_f))
     # 5. watertight, refined
-    wt_v, wt_f, _ = WT.watertight(_t(merged.vertices, np.float32), _faces(merged.triangles), res=wt_res, relax_iters=relax_iters)
+    wt_v, wt_f, _ = WT.watertight(_t(merged.vertices, np.float32), _faces(merged.triangles), res=wt_res, relax_iters=relax_iters, accel=field_accel)
     wt_v, wt_f, _ = MR.refine_long_edges(wt_v, wt_f, 4.0 / 3.0 * target_len, iterations=3)
     # 6. the head box, subdivided (the positions stay on the device; all_v_f.obj is written beside)
     sub_v, sub_f, _ = _subdivide(wt_v, wt_f, bbox_npz_path, root, head_threshold, head_iterations)

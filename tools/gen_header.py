@@ -20,6 +20,7 @@ GROUPS = {
     'bsdf.hip': 'render/renderutils/c_src/bsdf.cu + torch_bindings.cpp (lambert, frostbite, pbr_specular, pbr_bsdf, fresnel_shlick, ndf_ggx, lambda_ggx, masking_smith, each _{fwd,bwd}) with the semantics of the python twins render/renderutils/bsdf.py:57-151',
     'cubemap.hip': 'render/renderutils/c_src/cubemap.cu:110-169 (diffuse_cubemap_{fwd,bwd}), :246-350 (specular_cubemap_{fwd,bwd}) as driven by render/renderutils/ops.py:394-461; the backward as a gather',
     'bvh.hip': 'render/optixutils/c_src/optix_wrapper.cpp (optix_build_bvh: the OptiX acceleration structure) and the optixTrace of c_src/envsampling/kernel.cu:101-118 (any-hit shadow ray): a linear BVH built on the device and a stackless any-hit traversal -- the occlusion query is an entry point of its own',
+    'bvhdist.hip': 'the pysdf queries of geometry/hmsdf.py:236-237 and script/process_body_cloth_head_msdfcut.py:683,744 answered from the tree of bvh.hip instead of mesh_ops.hip\'s loop over every triangle: node moments, the exact nearest triangle of a point, and the winding-signed distance with a first-order hierarchical winding number (Barill et al. 2018)',
     'envshade.hip': 'render/optixutils/c_src/envsampling/kernel.cu:463-542 (__raygen__rg: importance-sampled environment shading with shadow rays) + torch_bindings.cpp (env_shade_{fwd,bwd}), shaded with c_src/bsdf.h; driven by render/optixutils/ops.py:81-108',
     'denoise.hip': 'render/optixutils/c_src/denoising.cu:14-130 (bilateral_denoiser_{fwd,bwd}_kernel) as driven by render/optixutils/ops.py:110-122,145-147; a two-image form for the demodulated path of render/render.py:134-136 (one set of guides)',
     'envlight.hip': 'render/light.py:46-59 (EnvironmentLight.update_pdf: the pdf of the lat-long map and the row / column CDFs the light sampler of envshade.hip searches)',
@@ -35,7 +36,7 @@ GROUPS = {
     'texmat.hip': 'the 2-D material lookups of shade(), render/render.py:277 (interpolate of v_tex by t_tex_idx) + render/texture.py:59-67 (Texture2D.sample of kd, ks, normal) at level 0: texel coordinate and up to three bilinear lookups per pixel in one pass, map gradients by fp32 atomics',
     'texmlp.hip': 'render/mlptexture.py:91-107 (MLPTexture3D.sample): tiny-cuda-nn HashGrid encoding (:62-79, un-vendored) + _MLP (:18-41) + sigmoid range map',
 }
-ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'envshade.hip', 'envlight.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'meshtopo.hip', 'meshrefine.hip', 'tetfill.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'uvatlas.hip', 'texmat.hip', 'optim.hip', 'timing.hip']
+ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'bvhdist.hip', 'envshade.hip', 'envlight.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'meshtopo.hip', 'meshrefine.hip', 'tetfill.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'uvatlas.hip', 'texmat.hip', 'optim.hip', 'timing.hip']
 head = '''/* d3h.h -- C ABI of libd3h_hip.so: the MI355X (gfx950) hot path of D3-Human's render-and-fit loop.
  * GENERATED by tools/gen_header.py from the extern "C" definitions in d3human-code_amd/csrc/ -- do not edit by hand.
  *
