@@ -6,7 +6,12 @@ here.  `script` is a namespace package (see connet_face_head.py): with both root
 
 The route, step by step (reference lines :613-747), and every deviation:
   1. "remesh" (remesh.mlx: MeshLab isotropic remeshing to 0.01, three iterations) is d3h.meshrefine.refine_long_edges(4/3 target_len, iterations=3): the
-     refine step alone.  There is no collapse, flip or tangential smoothing, so short edges stay and vertices are never moved.
+     refine step alone.  There is no collapse, flip or tangential smoothing, so short edges stay and vertices are never moved.  That is the default,
+     remesh='split'.  remesh='isotropic' runs d3h.meshrefine.isotropic_remesh(target_len, 3) in its place, here and in step 5: per iteration a split
+     above 4/3 target_len, collapses below 4/5 target_len, valence-improving flips, one tangential smoothing pass and the reprojection of every moved
+     vertex onto the input surface (one BVH per call).  What remains of the deviation: boundary and non-manifold vertices are pinned (MeshLab moves
+     boundary vertices along the boundary), independent operations are chosen by a deterministic minimum instead of MeshLab's sequential sweep, and
+     there is no adaptive length and no surface-distance check per operation.  process_subdivide (step 6) keeps its thresholded split either way.
   2. The garment is never made watertight and never extracted (wt.mlx: screened Poisson at depth 8, then pysdf): GarmentField answers the distance
      queries directly on the open garment, as -mesh_wsdf: distance to the nearest triangle, signed by the generalised winding number (|w| > 0.5 inside).
      field_accel='bvh' (default 'brute': the loop over every triangle) answers them, and the field of step 5, from a d3h.raytrace.Bvh: the garment's is
@@ -141,9 +146,15 @@ def _normals(v, f):
     return IO.auto_normals(_t(v, np.float32), _faces(f).int()).cpu().numpy()
 
 
-def _remesh(v, f, target_len):
-    v2, f2, _ = MR.refine_long_edges(_t(v, np.float32), _faces(f), 4.0 / 3.0 * target_len, iterations=3)
-    return v2, f2
+def _remesh_tensors(v, f, target_len, remesh):
+    """remesh='split': the refine step alone; 'isotropic': split, collapse, flip, smooth and reproject (d3h.meshrefine.isotropic_remesh)"""
+    if remesh == 'isotropic':
+        return MR.isotropic_remesh(v, f, target_len, 3)[:2]
+    return MR.refine_long_edges(v, f, 4.0 / 3.0 * target_len, iterations=3)[:2]
+
+
+def _remesh(v, f, target_len, remesh='split'):
+    return _remesh_tensors(_t(v, np.float32), _faces(f), target_len, remesh)
 
 
 def _head_faces(v, f, bbox_npz_path):
@@ -168,15 +179,17 @@ def process_subdivide(body_path, bbox_npz_path, root, script_root=None, local=Fa
 
 def process_body_msdf_distance_bodyedge(FLAGS, root, body_path, ori_cloth_path, smpl_cloth_path, smpl_path, bbox_npz_path, script_root="checkpoints/script",
                                         local=False, *, target_len=0.01, wt_res=128, relax_iters=32, head_threshold=0.002, head_iterations=3, push_eps=0.005,
-                                        push_margin=0.002, push_rounds=100, field_accel='brute'):
+                                        push_margin=0.002, push_rounds=100, field_accel='brute', remesh='split'):
+    if remesh not in ('split', 'isotropic'):
+        raise RuntimeError(f"process_body_msdf_distance_bodyedge: remesh must be 'split' or 'isotropic', got {remesh!r}")
     for p in (body_path, ori_cloth_path, smpl_cloth_path, smpl_path, bbox_npz_path):
         if not os.path.exists(p):
             raise FileNotFoundError(f'process_body_msdf_distance_bodyedge: {p} does not exist')
     os.makedirs(root, exist_ok=True)
 
     # 1. the garment and the SMPL part under it, refined
-    cloth_v, cloth_f = _remesh(*om_loadmesh(ori_cloth_path), target_len)
-    cut_v, cut_f = _remesh(*om_loadmesh(smpl_cloth_path), target_len)
+    cloth_v, cloth_f = _remesh(*om_loadmesh(ori_cloth_path), target_len, remesh)
+    cut_v, cut_f = _remesh(*om_loadmesh(smpl_cloth_path), target_len, remesh)
     # 2. the garment as a distance oracle
     garment = GarmentField(cloth_v.cpu().numpy(), cloth_f.cpu().numpy(), accel=field_accel)
     # 3. one ring off the cut SMPL, pushed under the garment
@@ -191,7 +204,7 @@ def process_body_msdf_distance_bodyedge(FLAGS, root, body_path, ori_cloth_path, 
     merged = merge_and_repair_meshes(MergedMesh(deformed_v, cut_f), MergedMesh(body_v, body_f))
     # 5. watertight, refined
     wt_v, wt_f, _ = WT.watertight(_t(merged.vertices, np.float32), _faces(merged.triangles), res=wt_res, relax_iters=relax_iters, accel=field_accel)
-    wt_v, wt_f, _ = MR.refine_long_edges(wt_v, wt_f, 4.0 / 3.0 * target_len, iterations=3)
+    wt_v, wt_f = _remesh_tensors(wt_v, wt_f, target_len, remesh)
     # 6. the head box, subdivided (the positions stay on the device; all_v_f.obj is written beside)
     sub_v, sub_f, _ = _subdivide(wt_v, wt_f, bbox_npz_path, root, head_threshold, head_iterations)
     # 7. body + garment under face labels, and the body vertices the garment covers
