@@ -1,5 +1,6 @@
-// composite.h -- shared by image_ops.hip (composite fwd / bwd) and raster.hip (the fused composite + antialias forward):
-// the per-buffer composite of a render layer (render/render.py:375-382,430-449) as a per-pixel function, and the LDS-staged row copies.
+// composite.h -- shared by image_ops.hip (composite fwd / bwd) and raster.hip (the fused composite + antialias pair and the layered
+// composite + antialias pair, forward and backward): the per-buffer composite of a render layer (render/render.py:375-382,430-449) as a
+// per-pixel function, the source description the entry points build from their host arrays, and the LDS-staged row copies.
 #pragma once
 #include "d3h_common.h"
 

@@ -1340,6 +1340,200 @@ __device__ __forceinline__ bool aa_on_discontinuity(const float* __restrict__ ra
 constexpr int AA_TILES = D3H_AA_TILES;
 constexpr int AA_WG_PIX = 256 * AA_TILES;
 
+// ---- what the six antialias kernels share ---------------------------------------------------------------------------------------------------
+// The three pairs of kernels differ in the pre-antialias image only: stored (aa_fwd / aa_bwd), composited on the fly from the layer buffers
+// (aa_composite_*), blended on the fly over `under` (layer_composite_*).  Each describes it as a functor `Pre`:
+//     Pre::At             what the image at a pixel depends on besides the channel (its index, coverage, weight)
+//     pre.at(p)           that, for pixel p of the frame
+//     pre.channels(fn)    calls fn(ch, val) for every channel ch of a row in turn; val(at) is the value of that channel at such a pixel
+// and everything else of phase 2 is written once, below.
+
+// A pixel of phase 2: its frame, the frame's slices of the inputs, and the four pairs it takes part in.
+struct AAPixel {
+    int b, x, y, self;                        // frame, column, row, y * W + x
+    size_t gb0;                               // global pixel index of the frame's first pixel
+    const float* rast_b;
+    const float* posb;
+    const unsigned char* flags_b;
+    AAPair pr[4];
+};
+
+// Set up pixel i (flat index over all frames: rows of consecutive frames are consecutive in memory).  Called by ALL lanes of a wave, in a loop
+// whose trip count is workgroup-uniform (aa_on_discontinuity is a wave-level operation); false: nothing to do for this pixel.  FWD: only the
+// pairs that blend INTO this pixel with a non-zero weight stay `ok` (the forward kernels rewrite their own pixel); otherwise all pairs do.
+template <bool FWD>
+__device__ __forceinline__ bool aa_pixel(AAPixel& px, size_t i, size_t n, const float* __restrict__ rast, const float* __restrict__ pos, int pos_bstride,
+                                         const int* __restrict__ tri, const unsigned char* __restrict__ flags, int nf, int H, int W) {
+    const size_t hw = (size_t)H * W;
+    int b = 0, x = 0, y = 0;
+    if (i < n) {
+        b = (int)(i / hw);
+        const int rem = (int)(i % hw);
+        y = rem / W; x = rem % W;
+    }
+    if (!aa_on_discontinuity(rast, i, i < n, x, y, H, W)) return false;
+    px.b = b; px.x = x; px.y = y; px.self = y * W + x;
+    px.gb0 = (size_t)b * hw;
+    px.rast_b = rast + 4 * px.gb0;
+    px.posb = pos + (size_t)b * pos_bstride;
+    px.flags_b = flags + (size_t)b * nf;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        px.pr[k] = aa_pair(px.rast_b, px.posb, tri, px.flags_b, x, y, k, H, W);
+        if (FWD) px.pr[k].ok = px.pr[k].ok && px.pr[k].self_is_dst && px.pr[k].wgt != 0.f;
+        any |= px.pr[k].ok;
+    }
+    return any;
+}
+
+// Forward, a pixel set up with FWD: orow[ch] = pre[self] + sum over its pairs of w (pre[other] - pre[self]), orow = the pixel's row of `out`.
+template <class Pre>
+__device__ __forceinline__ void aa_blend(const AAPixel& px, const Pre& pre, float* __restrict__ orow) {
+    const typename Pre::At self = pre.at(px.self);
+    typename Pre::At oth[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) oth[k] = px.pr[k].ok ? pre.at(px.pr[k].other) : typename Pre::At{};
+    pre.channels([&](int ch, auto val) {
+        const float base = val(self);
+        float v = base;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (px.pr[k].ok) v += px.pr[k].wgt * (val(oth[k]) - base);
+        orow[ch] = v;
+    });
+}
+
+// Backward: does any pair move this pixel's pre-antialias gradient away from g_out[self]?
+__device__ __forceinline__ bool aa_touched(const AAPixel& px) {
+    bool touch = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (px.pr[k].ok && px.pr[k].wgt != 0.f) touch = true;
+    return touch;
+}
+
+// Backward: the gradient of channel ch of this pixel's pre-antialias row, gathered (gb: the frame's g_out, C floats per pixel):
+// g[self] (1 - sum of the weights of the pairs that blend INTO self) + sum over the pairs that blend self into their other pixel q of w g[q]
+__device__ __forceinline__ float aa_gather(const AAPixel& px, const float* __restrict__ gb, int C, int ch) {
+    const float gs = gb[(size_t)px.self * C + ch];
+    float v = gs;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!px.pr[k].ok || px.pr[k].wgt == 0.f) continue;
+        if (px.pr[k].self_is_dst) v -= px.pr[k].wgt * gs;                                  // out[self] = ... - w pre[self]
+        else v += px.pr[k].wgt * gb[(size_t)px.pr[k].other * C + ch];                      // out[other] = ... + w pre[self]
+    }
+    return v;
+}
+
+// Backward: the position gradient of one pair, h its analysis, gd = d loss / d d (d = h.d, the crossing in units of the pixel distance);
+// dpb: the frame's slice of d_pos (float atomics).
+__device__ __forceinline__ void aa_pos_grad(const AAHit& h, int dirx, float gd, const float* __restrict__ posb, float* __restrict__ dpb, int H, int W) {
+    // d = (e - c_i) / (c_o - c_i) with c_o - c_i = +-1 along the pair axis; e = crossing coordinate
+    float px_i = (float)(h.pi % W) + 0.5f, py_i = (float)(h.pi / W) + 0.5f;
+    float px_o = (float)(h.po % W) + 0.5f, py_o = (float)(h.po / W) + 0.5f;
+    // edge end points in pixel coordinates, recomputed from the clip-space vertices
+    int vv[2] = {h.va, h.vb};
+    float4 pc[2];
+    float qv[2], ex[2], ey[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        pc[kk] = *(const float4*)(posb + 4 * (size_t)vv[kk]);
+        qv[kk] = 1.0f / pc[kk].w;
+        ex[kk] = (pc[kk].x * qv[kk] * 0.5f + 0.5f) * W;
+        ey[kk] = (pc[kk].y * qv[kk] * 0.5f + 0.5f) * H;
+    }
+    float gsx[2], gsy[2];
+    if (dirx) {
+        float ge = gd / (px_o - px_i);
+        float dy = ey[1] - ey[0];
+        float tt = (py_i - ey[0]) / dy;
+        // xe = xa + tt (xb - xa), tt = (cy - ya)/(yb - ya)
+        float gtt = ge * (ex[1] - ex[0]);
+        gsx[0] = ge * (1.f - tt); gsx[1] = ge * tt;
+        gsy[0] = gtt * (tt - 1.f) / dy;      // d tt/d ya = (tt - 1)/dy
+        gsy[1] = -gtt * tt / dy;             // d tt/d yb = -tt/dy
+    } else {
+        float ge = gd / (py_o - py_i);
+        float dx = ex[1] - ex[0];
+        float tt = (px_i - ex[0]) / dx;
+        float gtt = ge * (ey[1] - ey[0]);
+        gsy[0] = ge * (1.f - tt); gsy[1] = ge * tt;
+        gsx[0] = gtt * (tt - 1.f) / dx;
+        gsx[1] = -gtt * tt / dx;
+    }
+    // screen -> clip: sx = (x/w * .5 + .5) W
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        float q = qv[kk];
+        float gX = gsx[kk] * 0.5f * W, gY = gsy[kk] * 0.5f * H;
+        float* dp = dpb + 4 * (size_t)vv[kk];
+        atomicAdd(dp + 0, gX * q);
+        atomicAdd(dp + 1, gY * q);
+        atomicAdd(dp + 3, -(gX * pc[kk].x + gY * pc[kk].y) * q * q);
+    }
+}
+
+// Backward: the position gradient of the two pairs this pixel owns (right, down), added to d_pos (NULL: not wanted).  gb: the frame's g_out.
+template <class Pre>
+__device__ __forceinline__ void aa_owner_pairs_grad(const AAPixel& px, const Pre& pre, const float* gb, int C, const int* tri, float* d_pos, int pos_bstride,
+                                                    int H, int W) {
+    if (!d_pos) return;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!px.pr[k].ok) continue;
+        const int dirx = (k == 0) ? 1 : 0;
+        // analysed again rather than read back from pr[k].h: hipcc 7.2 (-O2 / -O3) mis-compiles the edge data when it travels through the
+        // struct array across the colour loop of the caller (wrong position gradients on the GPU, correct on the host build) -- the same
+        // defect round 1 hit with a struct returned from the analysis loop
+        const AAHit h = aa_analyse(px.rast_b, px.posb, tri, px.flags_b, px.x, px.y, dirx, H, W);
+        if (!h.ok) continue;
+        const float alpha = h.d - 0.5f;
+        // wgt = |d - 0.5|: d wgt / d d = sign(d - 0.5), and 0 AT d == 0.5 (torch's abs').  That case is not exotic -- d is a difference
+        // of pixel coordinates of magnitude 10^2..10^3, i.e. quantised to ~6e-5, so a few silhouette pairs per 10 renders sit exactly on
+        // the midpoint -- and it matters: the outer pixel then keeps an exactly-zero value, F.normalize / cosine_similarity of a zero
+        // normal hand back 1/eps-sized gradients (1e13) for it, and taking the +1 branch here sent them into the vertex positions
+        // (|d total / d sdf weights| ~ 1e15 once every few dozen iterations; the oracle chain on the same batch stays O(1)).
+        if (alpha == 0.f) continue;
+        const int dst = (alpha >= 0.f) ? h.po : h.pi;
+        const int src = (alpha >= 0.f) ? h.pi : h.po;
+        const typename Pre::At at_src = pre.at(src), at_dst = pre.at(dst);
+        float gw = 0.f;
+        pre.channels([&](int ch, auto val) {
+            const float g = gb[(size_t)dst * C + ch];
+            if (g != 0.f) gw = fmaf(g, val(at_src) - val(at_dst), gw);
+        });
+        if (gw == 0.f) continue;
+        aa_pos_grad(h, dirx, (alpha > 0.f) ? gw : -gw, px.posb, d_pos + (size_t)px.b * pos_bstride, H, W);
+    }
+}
+
+// Phase 1 of the two plain kernels: this workgroup's pixel range [p0, p0 + AA_WG_PIX) of a [n][C] image copied with 16-byte accesses, or
+// float by float where the range's float count or first float is no multiple of 4.
+__device__ __forceinline__ void aa_copy_pixels(float* __restrict__ dst, const float* __restrict__ src, size_t p0, size_t n, int C) {
+    const size_t cnt = (n - p0 < (size_t)AA_WG_PIX ? n - p0 : (size_t)AA_WG_PIX) * (size_t)C;   // floats of this workgroup's pixel range
+    src += p0 * C;
+    dst += p0 * C;
+    if ((cnt & 3) == 0 && ((p0 * C) & 3) == 0) {
+        for (size_t i = threadIdx.x; i < cnt / 4; i += 256) ((float4*)dst)[i] = ((const float4*)src)[i];
+    } else {
+        for (size_t i = threadIdx.x; i < cnt; i += 256) dst[i] = src[i];
+    }
+}
+
+// the stored image of the two plain kernels; cb: its frame, C floats per pixel
+struct AAStored {
+    using At = int;
+    const float* cb;
+    int C;
+    __device__ __forceinline__ At at(int p) const { return p; }
+    template <class Fn>
+    __device__ __forceinline__ void channels(Fn fn) const {
+        for (int c = 0; c < C; ++c) fn(c, [&](At p) { return cb[(size_t)p * C + c]; });
+    }
+};
+
 // Gather formulation: out[p] = color[p] + sum over the (at most four) pairs whose blended pixel is p of w (color[other] - color[p]).
 // One pass, no atomics, deterministic: every workgroup copies its 256 pixels x C floats with 16-byte accesses (phase 1: the whole
 // image except the ~1 % of pixels on an id discontinuity IS a copy), then the threads of pixels next to a discontinuity analyse their
@@ -1350,48 +1544,12 @@ __global__ __launch_bounds__(256) void aa_fwd_kernel(const float* __restrict__ c
                                                      int nb, int H, int W, int C, float* __restrict__ out) {
     const size_t n = (size_t)nb * H * W;
     const size_t p0 = (size_t)blockIdx.x * AA_WG_PIX;
-    const size_t cnt = (n - p0 < (size_t)AA_WG_PIX ? n - p0 : (size_t)AA_WG_PIX) * (size_t)C;   // floats of this workgroup's pixel range
-    const float* src = color + p0 * C;
-    float* dst = out + p0 * C;
-    if ((cnt & 3) == 0 && ((p0 * C) & 3) == 0) {
-        for (size_t i = threadIdx.x; i < cnt / 4; i += 256) ((float4*)dst)[i] = ((const float4*)src)[i];
-    } else {
-        for (size_t i = threadIdx.x; i < cnt; i += 256) dst[i] = src[i];
-    }
+    aa_copy_pixels(out, color, p0, n, C);
     __syncthreads();                       // phase 2 overwrites pixels phase 1 (other threads of this workgroup) has just written
-    for (int st = 0; st < AA_TILES; ++st) {         // (workgroup-uniform trip count: aa_on_discontinuity is a wave-level operation)
-        const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
-        int b = 0, x = 0, y = 0;
-        if (i < n) {
-            b = (int)(i / ((size_t)H * W));
-            const int rem = (int)(i % ((size_t)H * W));
-            y = rem / W; x = rem % W;
-        }
-        const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);     // (flat index: rows of consecutive frames are consecutive in memory)
-        if (!work) continue;
-        const float* rast_b = rast + 4 * (size_t)b * H * W;
-        const float* posb = pos + (size_t)b * pos_bstride;
-        const unsigned char* flags_b = flags + (size_t)b * nf;
-        const float* cb = color + (size_t)b * H * W * C;
-        float* ob = out + (size_t)b * H * W * C;
-        const int self = y * W + x;
-        AAPair pr[4];
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
-            pr[k].ok = pr[k].ok && pr[k].self_is_dst && pr[k].wgt != 0.f;
-            any |= pr[k].ok;
-        }
-        if (!any) continue;
-        for (int c = 0; c < C; ++c) {
-            const float base = cb[(size_t)self * C + c];
-            float v = base;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (pr[k].ok) v += pr[k].wgt * (cb[(size_t)pr[k].other * C + c] - base);
-            ob[(size_t)self * C + c] = v;
-        }
+    for (int st = 0; st < AA_TILES; ++st) {
+        AAPixel px;
+        if (!aa_pixel<true>(px, p0 + (size_t)st * 256 + threadIdx.x, n, rast, pos, pos_bstride, tri, flags, nf, H, W)) continue;
+        aa_blend(px, AAStored{color + px.gb0 * C, C}, out + (px.gb0 + px.self) * C);
     }
 }
 
@@ -1403,137 +1561,38 @@ __global__ __launch_bounds__(256) void aa_bwd_kernel(const float* __restrict__ c
                                                      float* __restrict__ g_color, float* __restrict__ d_pos) {
     const size_t n = (size_t)nb * H * W;
     const size_t p0 = (size_t)blockIdx.x * AA_WG_PIX;
-    const size_t cnt = (n - p0 < (size_t)AA_WG_PIX ? n - p0 : (size_t)AA_WG_PIX) * (size_t)C;
-    {
-        const float* src = g_out + p0 * C;
-        float* dst = g_color + p0 * C;
-        if ((cnt & 3) == 0 && ((p0 * C) & 3) == 0) {
-            for (size_t i = threadIdx.x; i < cnt / 4; i += 256) ((float4*)dst)[i] = ((const float4*)src)[i];
-        } else {
-            for (size_t i = threadIdx.x; i < cnt; i += 256) dst[i] = src[i];
-        }
-    }
+    aa_copy_pixels(g_color, g_out, p0, n, C);
     __syncthreads();
     for (int st = 0; st < AA_TILES; ++st) {
-    const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
-    int b = 0, x = 0, y = 0;
-    if (i < n) {
-        b = (int)(i / ((size_t)H * W));
-        const int rem = (int)(i % ((size_t)H * W));
-        y = rem / W; x = rem % W;
+        AAPixel px;
+        if (!aa_pixel<false>(px, p0 + (size_t)st * 256 + threadIdx.x, n, rast, pos, pos_bstride, tri, flags, nf, H, W)) continue;
+        const float* gb = g_out + px.gb0 * C;
+        if (aa_touched(px)) {
+            float* grow = g_color + (px.gb0 + px.self) * C;
+            for (int c = 0; c < C; ++c) grow[c] = aa_gather(px, gb, C, c);
+        }
+        aa_owner_pairs_grad(px, AAStored{color + px.gb0 * C, C}, gb, C, tri, d_pos, pos_bstride, H, W);
     }
-    const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);
-    if (!work) continue;
-    const float* rast_b = rast + 4 * (size_t)b * H * W;
-    const float* posb = pos + (size_t)b * pos_bstride;
-    const unsigned char* flags_b = flags + (size_t)b * nf;
-    const float* cb = color + (size_t)b * H * W * C;
-    const float* gb = g_out + (size_t)b * H * W * C;
-    float* gcb = g_color + (size_t)b * H * W * C;
-    const int self = y * W + x;
-    AAPair pr[4];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
-        any |= pr[k].ok;
-    }
-    if (!any) continue;
-    // ---- colour gradient of this pixel ----
-    {
-        float wsum = 0.f;
-        bool touch = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (pr[k].ok && pr[k].wgt != 0.f) { touch = true; if (pr[k].self_is_dst) wsum += pr[k].wgt; }
-        if (touch) {
-            for (int c = 0; c < C; ++c) {
-                const float gs = gb[(size_t)self * C + c];
-                float v = gs;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (!pr[k].ok || pr[k].wgt == 0.f) continue;
-                    if (pr[k].self_is_dst) v -= pr[k].wgt * gs;                                  // out[self] = ... - w color[self]
-                    else v += pr[k].wgt * gb[(size_t)pr[k].other * C + c];                       // out[other] = ... + w color[self]
-                }
-                gcb[(size_t)self * C + c] = v;
-            }
-        }
-        (void)wsum;
-    }
-    // ---- position gradient of the two pairs this pixel owns ----
-    if (!d_pos) continue;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (!pr[k].ok) continue;
-        const int dirx = (k == 0) ? 1 : 0;
-        // analysed again rather than read back from pr[k].h: hipcc 7.2 (-O2 / -O3) mis-compiles the edge data when it travels through the
-        // struct array across the colour loop above (wrong position gradients on the GPU, correct on the host build) -- the same defect
-        // round 1 hit with a struct returned from the analysis loop
-        const AAHit h = aa_analyse(rast_b, posb, tri, flags_b, x, y, dirx, H, W);
-        if (!h.ok) continue;
-        const float alpha = h.d - 0.5f;
-        // wgt = |d - 0.5|: d wgt / d d = sign(d - 0.5), and 0 AT d == 0.5 (torch's abs').  That case is not exotic -- d is a difference
-        // of pixel coordinates of magnitude 10^2..10^3, i.e. quantised to ~6e-5, so a few silhouette pairs per 10 renders sit exactly on
-        // the midpoint -- and it matters: the outer pixel then keeps an exactly-zero value, F.normalize / cosine_similarity of a zero
-        // normal hand back 1/eps-sized gradients (1e13) for it, and taking the +1 branch here sent them into the vertex positions
-        // (|d total / d sdf weights| ~ 1e15 once every few dozen iterations; the oracle chain on the same batch stays O(1)).
-        if (alpha == 0.f) continue;
-        const int dst = (alpha >= 0.f) ? h.po : h.pi;
-        const int src = (alpha >= 0.f) ? h.pi : h.po;
-        float gw = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float g = gb[(size_t)dst * C + c];
-            if (g != 0.f) gw = fmaf(g, cb[(size_t)src * C + c] - cb[(size_t)dst * C + c], gw);
-        }
-        if (gw == 0.f) continue;
-        const float gd = (alpha > 0.f) ? gw : -gw;
-        // d = (e - c_i) / (c_o - c_i) with c_o - c_i = +-1 along the pair axis; e = crossing coordinate
-        float px_i = (float)(h.pi % W) + 0.5f, py_i = (float)(h.pi / W) + 0.5f;
-        float px_o = (float)(h.po % W) + 0.5f, py_o = (float)(h.po / W) + 0.5f;
-        // edge end points in pixel coordinates, recomputed from the clip-space vertices
-        int vv[2] = {h.va, h.vb};
-        float4 pc[2];
-        float qv[2], ex[2], ey[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            pc[kk] = *(const float4*)(posb + 4 * (size_t)vv[kk]);
-            qv[kk] = 1.0f / pc[kk].w;
-            ex[kk] = (pc[kk].x * qv[kk] * 0.5f + 0.5f) * W;
-            ey[kk] = (pc[kk].y * qv[kk] * 0.5f + 0.5f) * H;
-        }
-        float gsx[2], gsy[2];
-        if (dirx) {
-            float ge = gd / (px_o - px_i);
-            float dy = ey[1] - ey[0];
-            float tt = (py_i - ey[0]) / dy;
-            // xe = xa + tt (xb - xa), tt = (cy - ya)/(yb - ya)
-            float gtt = ge * (ex[1] - ex[0]);
-            gsx[0] = ge * (1.f - tt); gsx[1] = ge * tt;
-            gsy[0] = gtt * (tt - 1.f) / dy;      // d tt/d ya = (tt - 1)/dy
-            gsy[1] = -gtt * tt / dy;             // d tt/d yb = -tt/dy
-        } else {
-            float ge = gd / (py_o - py_i);
-            float dx = ex[1] - ex[0];
-            float tt = (px_i - ex[0]) / dx;
-            float gtt = ge * (ey[1] - ey[0]);
-            gsy[0] = ge * (1.f - tt); gsy[1] = ge * tt;
-            gsx[0] = gtt * (tt - 1.f) / dx;
-            gsx[1] = -gtt * tt / dx;
-        }
-        // screen -> clip: sx = (x/w * .5 + .5) W
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            float q = qv[kk];
-            float gX = gsx[kk] * 0.5f * W, gY = gsy[kk] * 0.5f * H;
-            float* dp = d_pos + (size_t)b * pos_bstride + 4 * (size_t)vv[kk];
-            atomicAdd(dp + 0, gX * q);
-            atomicAdd(dp + 1, gY * q);
-            atomicAdd(dp + 3, -(gX * pc[kk].x + gY * pc[kk].y) * q * q);
-        }
-    }
-    }          // sub-tile loop
 }
+
+// the composite of the layer buffers, evaluated at the pixel (composite.h: comp_value)
+struct AAComposite {
+    struct At { size_t i; bool cov; };        // global pixel index, coverage
+    const CompArgs& a;
+    const float* rast_b;
+    size_t gb0, hw;
+    __device__ __forceinline__ At at(int p) const { return {gb0 + p, rast_b[4 * (size_t)p + 3] > 0.f}; }
+    template <class Fn>
+    __device__ __forceinline__ void channels(Fn fn) const {
+        int off = 0;
+        for (int s_ = 0; s_ < a.n; ++s_) {
+            const CompSrc& c = a.s[s_];
+            const int wch = c.kind == 3 ? 1 : c.nch + 1;
+            for (int j = 0; j < wch; ++j) fn(off + j, [&](const At& p) { return comp_value(c, j, p.i, p.cov, hw); });
+            off += wch;
+        }
+    }
+};
 
 // Composite + antialias in ONE forward pass (no gradient: the buffers of a render nobody differentiates -- the nine dead buffers of a
 // tick in its 'all' mode, the watertight validation render; render/render.py:375-382,430-449 run per buffer by the reference).  Phase 1
@@ -1558,47 +1617,9 @@ __global__ __launch_bounds__(256) void aa_composite_fwd_kernel(CompArgs a, const
     }
     __syncthreads();                       // phase 2 overwrites pixels phase 1 (other threads of this workgroup) has just written
     for (int st = 0; st < AA_TILES; ++st) {
-        const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
-        int b = 0, x = 0, y = 0;
-        if (i < n) {
-            b = (int)(i / hw);
-            const int rem = (int)(i % hw);
-            y = rem / W; x = rem % W;
-        }
-        const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);
-        if (!work) continue;
-        const float* rast_b = rast + 4 * (size_t)b * hw;
-        const float* posb = pos + (size_t)b * pos_bstride;
-        const unsigned char* flags_b = flags + (size_t)b * nf;
-        const size_t gb = (size_t)b * hw;                         // global pixel index of the frame's first pixel
-        const int self = y * W + x;
-        AAPair pr[4];
-        bool cov_o[4];
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
-            pr[k].ok = pr[k].ok && pr[k].self_is_dst && pr[k].wgt != 0.f;
-            cov_o[k] = pr[k].ok ? rast_b[4 * (size_t)pr[k].other + 3] > 0.f : false;
-            any |= pr[k].ok;
-        }
-        if (!any) continue;
-        const bool cov_s = rast_b[4 * (size_t)self + 3] > 0.f;
-        float* orow = out + (gb + self) * C;
-        int off = 0;
-        for (int s_ = 0; s_ < a.n; ++s_) {
-            const CompSrc& c = a.s[s_];
-            const int wch = c.kind == 3 ? 1 : c.nch + 1;
-            for (int j = 0; j < wch; ++j) {
-                const float base = comp_value(c, j, gb + self, cov_s, hw);
-                float v = base;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (pr[k].ok) v += pr[k].wgt * (comp_value(c, j, gb + pr[k].other, cov_o[k], hw) - base);
-                orow[off + j] = v;
-            }
-            off += wch;
-        }
+        AAPixel px;
+        if (!aa_pixel<true>(px, p0 + (size_t)st * 256 + threadIdx.x, n, rast, pos, pos_bstride, tri, flags, nf, H, W)) continue;
+        aa_blend(px, AAComposite{a, px.rast_b, px.gb0, hw}, out + (px.gb0 + px.self) * C);
     }
 }
 
@@ -1642,126 +1663,26 @@ __global__ __launch_bounds__(256) void aa_composite_bwd_kernel(CompArgs a, const
     }
     __syncthreads();                       // phase 2 overwrites entries phase 1 (other threads of this workgroup) has just written
     for (int st = 0; st < AA_TILES; ++st) {
-    const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
-    int b = 0, x = 0, y = 0;
-    if (i < n) {
-        b = (int)(i / hw);
-        const int rem = (int)(i % hw);
-        y = rem / W; x = rem % W;
-    }
-    const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);
-    if (!work) continue;
-    const float* rast_b = rast + 4 * (size_t)b * hw;
-    const float* posb = pos + (size_t)b * pos_bstride;
-    const unsigned char* flags_b = flags + (size_t)b * nf;
-    const size_t gb0 = (size_t)b * hw;                            // global pixel index of the frame's first pixel
-    const float* gb = g_out + gb0 * C;
-    const int self = y * W + x;
-    AAPair pr[4];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
-        any |= pr[k].ok;
-    }
-    if (!any) continue;
-    // ---- gradient of this pixel's stacked colour, sliced per source under its coverage ----
-    {
-        bool touch = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (pr[k].ok && pr[k].wgt != 0.f) touch = true;
-        if (touch) {
-            const bool cov_s = rast_b[4 * (size_t)self + 3] > 0.f;
+        AAPixel px;
+        if (!aa_pixel<false>(px, p0 + (size_t)st * 256 + threadIdx.x, n, rast, pos, pos_bstride, tri, flags, nf, H, W)) continue;
+        const float* gb = g_out + px.gb0 * C;
+        // ---- gradient of this pixel's stacked colour, sliced per source under its coverage ----
+        if (aa_touched(px)) {
+            const bool cov_s = px.rast_b[4 * (size_t)px.self + 3] > 0.f;
             int off = 0;
             for (int s_ = 0; s_ < a.n; ++s_) {
                 const CompSrc& c = a.s[s_];
                 if (c.d) {
                     for (int j = 0; j < c.nch; ++j) {
-                        const float gs = gb[(size_t)self * C + off + j];
-                        float v = gs;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (!pr[k].ok || pr[k].wgt == 0.f) continue;
-                            if (pr[k].self_is_dst) v -= pr[k].wgt * gs;
-                            else v += pr[k].wgt * gb[(size_t)pr[k].other * C + off + j];
-                        }
-                        c.d[(gb0 + self) * c.dch + j] = cov_s ? v : 0.f;
+                        const float v = aa_gather(px, gb, C, off + j);
+                        c.d[(px.gb0 + px.self) * c.dch + j] = cov_s ? v : 0.f;
                     }
                 }
                 off += c.kind == 3 ? 1 : c.nch + 1;
             }
         }
+        aa_owner_pairs_grad(px, AAComposite{a, px.rast_b, px.gb0, hw}, gb, C, tri, d_pos, pos_bstride, H, W);
     }
-    // ---- position gradient of the two pairs this pixel owns ----
-    if (!d_pos) continue;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (!pr[k].ok) continue;
-        const int dirx = (k == 0) ? 1 : 0;
-        const AAHit h = aa_analyse(rast_b, posb, tri, flags_b, x, y, dirx, H, W);      // (analysed again: see aa_bwd_kernel)
-        if (!h.ok) continue;
-        const float alpha = h.d - 0.5f;
-        if (alpha == 0.f) continue;                                                   // (see aa_bwd_kernel)
-        const int dst = (alpha >= 0.f) ? h.po : h.pi;
-        const int src = (alpha >= 0.f) ? h.pi : h.po;
-        const bool cov_src = rast_b[4 * (size_t)src + 3] > 0.f, cov_dst = rast_b[4 * (size_t)dst + 3] > 0.f;
-        float gw = 0.f;
-        {
-            int off = 0;
-            for (int s_ = 0; s_ < a.n; ++s_) {
-                const CompSrc& c = a.s[s_];
-                const int wch = c.kind == 3 ? 1 : c.nch + 1;
-                for (int j = 0; j < wch; ++j) {
-                    const float g = gb[(size_t)dst * C + off + j];
-                    if (g != 0.f) gw = fmaf(g, comp_value(c, j, gb0 + src, cov_src, hw) - comp_value(c, j, gb0 + dst, cov_dst, hw), gw);
-                }
-                off += wch;
-            }
-        }
-        if (gw == 0.f) continue;
-        const float gd = (alpha > 0.f) ? gw : -gw;
-        float px_i = (float)(h.pi % W) + 0.5f, py_i = (float)(h.pi / W) + 0.5f;
-        float px_o = (float)(h.po % W) + 0.5f, py_o = (float)(h.po / W) + 0.5f;
-        int vv[2] = {h.va, h.vb};
-        float4 pc[2];
-        float qv[2], ex[2], ey[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            pc[kk] = *(const float4*)(posb + 4 * (size_t)vv[kk]);
-            qv[kk] = 1.0f / pc[kk].w;
-            ex[kk] = (pc[kk].x * qv[kk] * 0.5f + 0.5f) * W;
-            ey[kk] = (pc[kk].y * qv[kk] * 0.5f + 0.5f) * H;
-        }
-        float gsx[2], gsy[2];
-        if (dirx) {
-            float ge = gd / (px_o - px_i);
-            float dy = ey[1] - ey[0];
-            float tt = (py_i - ey[0]) / dy;
-            float gtt = ge * (ex[1] - ex[0]);
-            gsx[0] = ge * (1.f - tt); gsx[1] = ge * tt;
-            gsy[0] = gtt * (tt - 1.f) / dy;
-            gsy[1] = -gtt * tt / dy;
-        } else {
-            float ge = gd / (py_o - py_i);
-            float dx = ex[1] - ex[0];
-            float tt = (px_i - ex[0]) / dx;
-            float gtt = ge * (ey[1] - ey[0]);
-            gsy[0] = ge * (1.f - tt); gsy[1] = ge * tt;
-            gsx[0] = gtt * (tt - 1.f) / dx;
-            gsx[1] = -gtt * tt / dx;
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            float q = qv[kk];
-            float gX = gsx[kk] * 0.5f * W, gY = gsy[kk] * 0.5f * H;
-            float* dp = d_pos + (size_t)b * pos_bstride + 4 * (size_t)vv[kk];
-            atomicAdd(dp + 0, gX * q);
-            atomicAdd(dp + 1, gY * q);
-            atomicAdd(dp + 3, -(gX * pc[kk].x + gY * pc[kk].y) * q * q);
-        }
-    }
-    }          // sub-tile loop
 }
 
 // ---- one step of layered compositing (depth peeling, render/render.py:375-382 with more than one layer) ---------------------------------
@@ -1781,6 +1702,30 @@ __device__ __forceinline__ float layer_value(const CompSrc& c, int j, size_t i, 
     if (c.kind == 3) return layer_lerp(u[0], 1.0f, c.p[i * c.stride]);
     return layer_lerp(u[j], j < c.nch ? c.p[i * c.stride + j] : 1.0f, w);
 }
+
+// the layer blended over `under`, evaluated at the pixel
+struct AALayer {
+    struct At { size_t i; bool cov; float w; };       // global pixel index, coverage, alpha where covered
+    const CompArgs& a;
+    const float* alpha;
+    const float* under;
+    const float* rast_b;
+    size_t gb0;
+    __device__ __forceinline__ At at(int p) const {
+        const bool cov = rast_b[4 * (size_t)p + 3] > 0.f;
+        return {gb0 + p, cov, (cov && alpha) ? alpha[gb0 + p] : 1.0f};
+    }
+    template <class Fn>
+    __device__ __forceinline__ void channels(Fn fn) const {
+        int off = 0;
+        for (int s_ = 0; s_ < a.n; ++s_) {
+            const CompSrc& c = a.s[s_];
+            const int wch = c.kind == 3 ? 1 : c.nch + 1;
+            for (int j = 0; j < wch; ++j) fn(off + j, [&](const At& p) { return layer_value(c, j, p.i, p.cov, p.w, under + p.i * a.C + off); });
+            off += wch;
+        }
+    }
+};
 
 __global__ __launch_bounds__(256) void layer_composite_fwd_kernel(CompArgs a, const float* __restrict__ alpha, const float* __restrict__ under,
                                                                   const float* __restrict__ rast, const float* __restrict__ pos, int pos_bstride,
@@ -1810,50 +1755,9 @@ __global__ __launch_bounds__(256) void layer_composite_fwd_kernel(CompArgs a, co
     }
     __syncthreads();                       // phase 2 overwrites pixels phase 1 (other threads of this workgroup) has just written
     for (int st = 0; st < AA_TILES; ++st) {
-        const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
-        int b = 0, x = 0, y = 0;
-        if (i < n) {
-            b = (int)(i / hw);
-            const int rem = (int)(i % hw);
-            y = rem / W; x = rem % W;
-        }
-        const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);
-        if (!work) continue;
-        const float* rast_b = rast + 4 * (size_t)b * hw;
-        const float* posb = pos + (size_t)b * pos_bstride;
-        const unsigned char* flags_b = flags + (size_t)b * nf;
-        const size_t gb = (size_t)b * hw;                         // global pixel index of the frame's first pixel
-        const int self = y * W + x;
-        AAPair pr[4];
-        bool cov_o[4];
-        float w_o[4];
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
-            pr[k].ok = pr[k].ok && pr[k].self_is_dst && pr[k].wgt != 0.f;
-            cov_o[k] = pr[k].ok ? rast_b[4 * (size_t)pr[k].other + 3] > 0.f : false;
-            w_o[k] = (cov_o[k] && alpha) ? alpha[gb + pr[k].other] : 1.0f;
-            any |= pr[k].ok;
-        }
-        if (!any) continue;
-        const bool cov_s = rast_b[4 * (size_t)self + 3] > 0.f;
-        const float w_s = (cov_s && alpha) ? alpha[gb + self] : 1.0f;
-        float* orow = out + (gb + self) * C;
-        int off = 0;
-        for (int s_ = 0; s_ < a.n; ++s_) {
-            const CompSrc& c = a.s[s_];
-            const int wch = c.kind == 3 ? 1 : c.nch + 1;
-            for (int j = 0; j < wch; ++j) {
-                const float base = layer_value(c, j, gb + self, cov_s, w_s, under + (gb + self) * C + off);
-                float v = base;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (pr[k].ok) v += pr[k].wgt * (layer_value(c, j, gb + pr[k].other, cov_o[k], w_o[k], under + (gb + pr[k].other) * C + off) - base);
-                orow[off + j] = v;
-            }
-            off += wch;
-        }
+        AAPixel px;
+        if (!aa_pixel<true>(px, p0 + (size_t)st * 256 + threadIdx.x, n, rast, pos, pos_bstride, tri, flags, nf, H, W)) continue;
+        aa_blend(px, AALayer{a, alpha, under, px.rast_b, px.gb0}, out + (px.gb0 + px.self) * C);
     }
 }
 
@@ -1911,138 +1815,37 @@ __global__ __launch_bounds__(256) void layer_composite_bwd_kernel(CompArgs a, co
     }
     __syncthreads();                       // phase 2 overwrites entries phase 1 (other threads of this workgroup) has just written
     for (int st = 0; st < AA_TILES; ++st) {
-    const size_t i = p0 + (size_t)st * 256 + threadIdx.x;
-    int b = 0, x = 0, y = 0;
-    if (i < n) {
-        b = (int)(i / hw);
-        const int rem = (int)(i % hw);
-        y = rem / W; x = rem % W;
-    }
-    const bool work = aa_on_discontinuity(rast, i, i < n, x, y, H, W);
-    if (!work) continue;
-    const float* rast_b = rast + 4 * (size_t)b * hw;
-    const float* posb = pos + (size_t)b * pos_bstride;
-    const unsigned char* flags_b = flags + (size_t)b * nf;
-    const size_t gb0 = (size_t)b * hw;                            // global pixel index of the frame's first pixel
-    const float* gb = g_out + gb0 * C;
-    const int self = y * W + x;
-    AAPair pr[4];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        pr[k] = aa_pair(rast_b, posb, tri, flags_b, x, y, k, H, W);
-        any |= pr[k].ok;
-    }
-    if (!any) continue;
-    // ---- this pixel's gradients again, from the gathered gradient of its pre-antialias row ----
-    {
-        bool touch = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (pr[k].ok && pr[k].wgt != 0.f) touch = true;
-        if (touch) {
-            const bool cov_s = rast_b[4 * (size_t)self + 3] > 0.f;
-            const float w_s = cov_s ? (alpha ? alpha[gb0 + self] : 1.0f) : 0.f;
-            const float* u = under + (gb0 + self) * C;
+        AAPixel px;
+        if (!aa_pixel<false>(px, p0 + (size_t)st * 256 + threadIdx.x, n, rast, pos, pos_bstride, tri, flags, nf, H, W)) continue;
+        const float* gb = g_out + px.gb0 * C;
+        // ---- this pixel's gradients again, from the gathered gradient of its pre-antialias row ----
+        if (aa_touched(px)) {
+            const size_t is = px.gb0 + px.self;
+            const bool cov_s = px.rast_b[4 * (size_t)px.self + 3] > 0.f;
+            const float w_s = cov_s ? (alpha ? alpha[is] : 1.0f) : 0.f;
+            const float* u = under + is * C;
             int off = 0;
             float da = 0.f;
             for (int s_ = 0; s_ < a.n; ++s_) {
                 const CompSrc& c = a.s[s_];
                 const int wch = c.kind == 3 ? 1 : c.nch + 1;
                 for (int j = 0; j < wch; ++j) {
-                    const float gs = gb[(size_t)self * C + off + j];
-                    float v = gs;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (!pr[k].ok || pr[k].wgt == 0.f) continue;
-                        if (pr[k].self_is_dst) v -= pr[k].wgt * gs;
-                        else v += pr[k].wgt * gb[(size_t)pr[k].other * C + off + j];
-                    }
+                    const float v = aa_gather(px, gb, C, off + j);
                     if (c.kind == 3) {
-                        if (c.d) c.d[(gb0 + self) * c.dch] = cov_s ? v * (1.0f - u[off]) : 0.f;
-                        if (d_under) d_under[(gb0 + self) * C + off] = v * (1.0f - (cov_s ? c.p[(gb0 + self) * c.stride] : 0.f));
+                        if (c.d) c.d[is * c.dch] = cov_s ? v * (1.0f - u[off]) : 0.f;
+                        if (d_under) d_under[is * C + off] = v * (1.0f - (cov_s ? c.p[is * c.stride] : 0.f));
                     } else {
-                        if (j < c.nch && c.d) c.d[(gb0 + self) * c.dch + j] = v * w_s;
-                        if (d_alpha && cov_s) da += v * ((j < c.nch ? c.p[(gb0 + self) * c.stride + j] : 1.0f) - u[off + j]);
-                        if (d_under) d_under[(gb0 + self) * C + off + j] = v * (1.0f - w_s);
+                        if (j < c.nch && c.d) c.d[is * c.dch + j] = v * w_s;
+                        if (d_alpha && cov_s) da += v * ((j < c.nch ? c.p[is * c.stride + j] : 1.0f) - u[off + j]);
+                        if (d_under) d_under[is * C + off + j] = v * (1.0f - w_s);
                     }
                 }
                 off += wch;
             }
-            if (d_alpha) d_alpha[gb0 + self] = da;
+            if (d_alpha) d_alpha[is] = da;
         }
+        aa_owner_pairs_grad(px, AALayer{a, alpha, under, px.rast_b, px.gb0}, gb, C, tri, d_pos, pos_bstride, H, W);
     }
-    // ---- position gradient of the two pairs this pixel owns ----
-    if (!d_pos) continue;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (!pr[k].ok) continue;
-        const int dirx = (k == 0) ? 1 : 0;
-        const AAHit h = aa_analyse(rast_b, posb, tri, flags_b, x, y, dirx, H, W);      // (analysed again: see aa_bwd_kernel)
-        if (!h.ok) continue;
-        const float alpha_d = h.d - 0.5f;
-        if (alpha_d == 0.f) continue;                                                 // (see aa_bwd_kernel)
-        const int dst = (alpha_d >= 0.f) ? h.po : h.pi;
-        const int src = (alpha_d >= 0.f) ? h.pi : h.po;
-        const bool cov_src = rast_b[4 * (size_t)src + 3] > 0.f, cov_dst = rast_b[4 * (size_t)dst + 3] > 0.f;
-        const float w_src = (cov_src && alpha) ? alpha[gb0 + src] : 1.0f, w_dst = (cov_dst && alpha) ? alpha[gb0 + dst] : 1.0f;
-        float gw = 0.f;
-        {
-            int off = 0;
-            for (int s_ = 0; s_ < a.n; ++s_) {
-                const CompSrc& c = a.s[s_];
-                const int wch = c.kind == 3 ? 1 : c.nch + 1;
-                for (int j = 0; j < wch; ++j) {
-                    const float g = gb[(size_t)dst * C + off + j];
-                    if (g != 0.f) gw = fmaf(g, layer_value(c, j, gb0 + src, cov_src, w_src, under + (gb0 + src) * C + off)
-                                               - layer_value(c, j, gb0 + dst, cov_dst, w_dst, under + (gb0 + dst) * C + off), gw);
-                }
-                off += wch;
-            }
-        }
-        if (gw == 0.f) continue;
-        const float gd = (alpha_d > 0.f) ? gw : -gw;
-        float px_i = (float)(h.pi % W) + 0.5f, py_i = (float)(h.pi / W) + 0.5f;
-        float px_o = (float)(h.po % W) + 0.5f, py_o = (float)(h.po / W) + 0.5f;
-        int vv[2] = {h.va, h.vb};
-        float4 pc[2];
-        float qv[2], ex[2], ey[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            pc[kk] = *(const float4*)(posb + 4 * (size_t)vv[kk]);
-            qv[kk] = 1.0f / pc[kk].w;
-            ex[kk] = (pc[kk].x * qv[kk] * 0.5f + 0.5f) * W;
-            ey[kk] = (pc[kk].y * qv[kk] * 0.5f + 0.5f) * H;
-        }
-        float gsx[2], gsy[2];
-        if (dirx) {
-            float ge = gd / (px_o - px_i);
-            float dy = ey[1] - ey[0];
-            float tt = (py_i - ey[0]) / dy;
-            float gtt = ge * (ex[1] - ex[0]);
-            gsx[0] = ge * (1.f - tt); gsx[1] = ge * tt;
-            gsy[0] = gtt * (tt - 1.f) / dy;
-            gsy[1] = -gtt * tt / dy;
-        } else {
-            float ge = gd / (py_o - py_i);
-            float dx = ex[1] - ex[0];
-            float tt = (px_i - ex[0]) / dx;
-            float gtt = ge * (ey[1] - ey[0]);
-            gsy[0] = ge * (1.f - tt); gsy[1] = ge * tt;
-            gsx[0] = gtt * (tt - 1.f) / dx;
-            gsx[1] = -gtt * tt / dx;
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            float q = qv[kk];
-            float gX = gsx[kk] * 0.5f * W, gY = gsy[kk] * 0.5f * H;
-            float* dp = d_pos + (size_t)b * pos_bstride + 4 * (size_t)vv[kk];
-            atomicAdd(dp + 0, gX * q);
-            atomicAdd(dp + 1, gY * q);
-            atomicAdd(dp + 3, -(gX * pc[kk].x + gY * pc[kk].y) * q * q);
-        }
-    }
-    }          // sub-tile loop
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2382,6 +2185,12 @@ extern "C" int d3h_antialias_fwd(const float* color, const float* rast, const fl
     return D3H_OK;
 }
 
+// the frame and mesh arguments of the four fused entry points: refused?  (nf == 0 is allowed without pos / tri / flags: an empty mesh has no
+// triangles, nothing is covered, nothing to blend)
+static inline bool aa_frame_args_bad(int nb, int H, int W, int nf, const float* pos, const int* tri, const unsigned char* flags) {
+    return nb < 0 || H <= 0 || W <= 0 || nf < 0 || (nf > 0 && (!pos || !tri || !flags));
+}
+
 // Composite (d3h_composite_fwd: same source description, host arrays read before the call returns) AND antialias (d3h_antialias_fwd:
 // flags from d3h_antialias_flags) in one forward pass; out [nb][H][W][C], C = sum(nch + 1) (kind 3: 1).  No backward: for renders nobody
 // differentiates.  Bit-identical to the two separate calls.
@@ -2390,7 +2199,7 @@ extern "C" int d3h_composite_antialias_fwd(int nsrc, const float* const* src, co
                                            const int* tri, int nf, const unsigned char* flags, int nb, int H, int W, float* out, void* stream) {
     CompArgs a;
     int rc = comp_args(a, nsrc, src, nullptr, stride, nch, kind, bg, bg_batched, true);
-    if (rc != D3H_OK || !src || !rast || !out || nb < 0 || H <= 0 || W <= 0 || nf < 0 || (nf > 0 && (!pos || !tri || !flags))) return D3H_ERR_ARG;     // (an empty mesh has no triangles: nothing is covered, nothing to blend)
+    if (rc != D3H_OK || !src || !rast || !out || aa_frame_args_bad(nb, H, W, nf, pos, tri, flags)) return D3H_ERR_ARG;
     for (int k = 0; k < nsrc; ++k) if (!src[k]) return D3H_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     size_t n = (size_t)nb * H * W;
@@ -2413,7 +2222,7 @@ extern "C" int d3h_composite_antialias_bwd(int nsrc, const float* const* src, fl
                                            void* stream) {
     CompArgs a;
     int rc = comp_args(a, nsrc, src, dsrc, stride, nch, kind, bg, bg_batched, true, dch);
-    if (rc != D3H_OK || !src || !dsrc || !rast || !g_out || nb < 0 || H <= 0 || W <= 0 || nf < 0 || (nf > 0 && (!pos || !tri || !flags))) return D3H_ERR_ARG;
+    if (rc != D3H_OK || !src || !dsrc || !rast || !g_out || aa_frame_args_bad(nb, H, W, nf, pos, tri, flags)) return D3H_ERR_ARG;
     int maxch = 1;
     for (int k = 0; k < nsrc; ++k) {
         if (!src[k]) return D3H_ERR_ARG;
@@ -2440,7 +2249,7 @@ extern "C" int d3h_layer_composite_antialias_fwd(int nsrc, const float* const* s
                                                  const int* tri, int nf, const unsigned char* flags, int nb, int H, int W, float* out, void* stream) {
     CompArgs a;
     int rc = comp_args(a, nsrc, src, nullptr, stride, nch, kind, nullptr, nullptr, false);
-    if (rc != D3H_OK || !src || !under || !rast || !out || out == under || nb < 0 || H <= 0 || W <= 0 || nf < 0 || (nf > 0 && (!pos || !tri || !flags)))
+    if (rc != D3H_OK || !src || !under || !rast || !out || out == under || aa_frame_args_bad(nb, H, W, nf, pos, tri, flags))
         return D3H_ERR_ARG;
     for (int k = 0; k < nsrc; ++k) if (!src[k]) return D3H_ERR_ARG;
     const size_t lds = (size_t)256 * a.C * sizeof(float);
@@ -2467,7 +2276,7 @@ extern "C" int d3h_layer_composite_antialias_bwd(int nsrc, const float* const* s
                                                  const float* g_out, float* d_alpha, float* d_under, float* d_pos, void* stream) {
     CompArgs a;
     int rc = comp_args(a, nsrc, src, dsrc, stride, nch, kind, nullptr, nullptr, false, dch);
-    if (rc != D3H_OK || !src || !under || !rast || !g_out || d_under == g_out || nb < 0 || H <= 0 || W <= 0 || nf < 0 || (nf > 0 && (!pos || !tri || !flags)))
+    if (rc != D3H_OK || !src || !under || !rast || !g_out || d_under == g_out || aa_frame_args_bad(nb, H, W, nf, pos, tri, flags))
         return D3H_ERR_ARG;
     int maxch = 1;
     for (int k = 0; k < nsrc; ++k) {

@@ -292,26 +292,30 @@ def composite_antialias(rast, sources, pos, tri):
     """antialias(composite(rast, sources), rast, pos, tri) in ONE forward pass (csrc/raster.hip:aa_composite_fwd_kernel), for renders
     nobody differentiates: the dead buffers of a tick in its 'all' mode, the watertight validation render.  Bit-identical to the two
     separate ops; no autograd (call it under torch.no_grad())."""
-    import ctypes
-    from . import raster as _R
     assert not torch.is_grad_enabled() or not any(s.requires_grad for s, _, _ in sources), 'composite_antialias is forward-only'
     B, H, W = rast.shape[:3]
-    dev = rast.device
-    n = len(sources)
     srcs = [s.expand(B, H, W, s.shape[-1]) for s, _, _ in sources]
-    kinds = [k for _, k, _ in sources]
-    views = [_pix_view(s) for s in srcs]
-    nch = [int(s.shape[-1]) for s in srcs]
+    return _composite_antialias_fwd(rast, pos, tri, [k for _, k, _ in sources], [b for _, _, b in sources], [_pix_view(s) for s in srcs])[0]
+
+
+def _composite_antialias_fwd(rast, pos, tri, kinds, bgs, views):
+    """the one call of composite_antialias_fwd; views: _pix_view of every source -> (out, what the backward needs of the prepared arguments:
+    rast, pos, tri, flags, backgrounds, channels per source)"""
+    import ctypes
+    from . import raster as _R
+    B, H, W = rast.shape[:3]
+    n = len(views)
+    nch = [int(v[0].shape[-1]) for v in views]
     C = sum(1 if k == COMP_ALPHA else c + 1 for k, c in zip(kinds, nch))
-    out = torch.empty(B, H, W, C, dtype=torch.float32, device=dev)
-    bg_t = [None if b is None else b.float().contiguous() for _, _, b in sources]
+    out = torch.empty(B, H, W, C, dtype=torch.float32, device=rast.device)
+    bg_t = [None if b is None else b.float().contiguous() for b in bgs]
     rc, pos_c, tri_c = rast.contiguous(), pos.contiguous().float(), tri.contiguous()
     flags = _R._edge_flags(pos_c, tri_c, B, H, W)
     I = ctypes.c_int * n
     L.call('composite_antialias_fwd', n, L.ptr_array([v[0] for v in views], strided=True), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
            L.ptr_array(bg_t), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]), rc, pos_c, _R._bstride(pos_c), tri_c,
            tri_c.shape[0], flags, B, H, W, out)
-    return out
+    return out, (rc, pos_c, tri_c, flags, bg_t, nch)
 
 
 class _CompositeAntialiasFn(torch.autograd.Function):
@@ -322,21 +326,8 @@ class _CompositeAntialiasFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rast, pos, tri, kinds, bgs, use, *srcs):
-        import ctypes
-        from . import raster as _R
-        B, H, W = rast.shape[:3]
-        n = len(srcs)
         views = [_pix_view(s if not u else s[..., :u]) for s, u in zip(srcs, use)]
-        nch = [int(v[0].shape[-1]) for v in views]
-        C = sum(1 if k == COMP_ALPHA else c + 1 for k, c in zip(kinds, nch))
-        out = torch.empty(B, H, W, C, dtype=torch.float32, device=rast.device)
-        bg_t = [None if b is None else b.float().contiguous() for b in bgs]
-        rc, pos_c, tri_c = rast.contiguous(), pos.contiguous().float(), tri.contiguous()
-        flags = _R._edge_flags(pos_c, tri_c, B, H, W)
-        I = ctypes.c_int * n
-        L.call('composite_antialias_fwd', n, L.ptr_array([v[0] for v in views], strided=True), I(*[int(v[1]) for v in views]), I(*nch), I(*kinds),
-               L.ptr_array(bg_t), I(*[0 if b is None or b.shape[0] == 1 else 1 for b in bg_t]), rc, pos_c, _R._bstride(pos_c), tri_c,
-               tri_c.shape[0], flags, B, H, W, out)
+        out, (rc, pos_c, tri_c, flags, bg_t, nch) = _composite_antialias_fwd(rast, pos, tri, kinds, bgs, views)
         ctx.save_for_backward(rc, pos_c, tri_c, flags, *[v[0] for v in views], *[b for b in bg_t if b is not None])
         ctx.meta = (kinds, nch, [s.shape for s in srcs], [int(v[1]) for v in views], [b is not None for b in bg_t])
         return out

@@ -515,6 +515,43 @@ def check_aa_shapes_reach_the_scalar_branch():
     assert len(odd) >= 3, odd
 
 
+def check_aa_three_routes_agree_bit_for_bit(dev):
+    """EMULATION ONLY (it runs the blocks serially, so the float atomics of d_pos come in one order; on the GPU they do not).  The same
+    pre-antialias image by the three pairs of kernels: antialias(composite(...)), composite_antialias_grad, and layer_composite_antialias with
+    alpha=None over under = zeros.  Two COMP_ZERO sources of 3 and 2 channels: composite writes [src, 1] where covered and 0 elsewhere, the
+    layer's two-branch lerp is exact at weight 1 (covered) and 0 (not), so all three see the same image and share every later operation:
+    outputs and d_pos are equal bit for bit.  Nothing else ties the layer kernel's position gradient to the other two."""
+    from d3h import imgops as I, raster
+    from oracle import raster as OR
+    H = W = 40
+    posn, f = _raster_scene(40, 2)
+    tri_o, tri = torch.from_numpy(f), T(f.astype(np.int32), dev)
+    rast_o, _ = OR.rasterize(torch.from_numpy(posn), tri_o, H, W)
+    rast = rast_o.to(dev).contiguous()
+    gen = torch.Generator().manual_seed(77)
+    srcn = [torch.randn(2, H, W, 3, generator=gen), torch.randn(2, H, W, 2, generator=gen)]
+    G = torch.randn(2, H, W, 7, generator=gen).to(dev)
+    outs, dpos = [], []
+    for route in range(3):
+        srcs = [(s.clone().to(dev).requires_grad_(True), COMP_ZERO, None) for s in srcn]
+        pos = T(posn, dev, True)
+        if route == 0:
+            out = raster.antialias(I.composite(rast, srcs), rast, pos, tri)
+        elif route == 1:
+            out = I.composite_antialias_grad(rast, srcs, pos, tri)
+        else:
+            out = I.layer_composite_antialias(rast, srcs, None, torch.zeros(2, H, W, 7, device=dev), pos, tri)
+        (out * G).sum().backward()
+        outs.append(out.detach())
+        dpos.append(pos.grad)
+    nz = int((dpos[0] != 0).sum())
+    print(f'[raster64] {dev:4s} three routes: {nz} non-zero d_pos entries')
+    assert tuple(outs[0].shape) == (2, H, W, 7) and nz > 0
+    for k in (1, 2):
+        assert torch.equal(outs[k], outs[0]), k
+        assert torch.equal(dpos[k], dpos[0]), k
+
+
 def _quad(px, H, W, z=0.1):
     """four pixel-space corners -> clip positions [4, 4] with w = 1"""
     return np.array([[x / W * 2 - 1, y / H * 2 - 1, z, 1.0] for x, y in px], np.float32)

@@ -36,6 +36,10 @@ def test_emul_antialias_nothing_blends_across_the_frame_boundary(emul):
     RC.check_aa_frame_boundary(emul)
 
 
+def test_emul_antialias_three_routes_to_one_image_agree_bit_for_bit(emul):
+    RC.check_aa_three_routes_agree_bit_for_bit(emul)
+
+
 def test_emul_raster64_large_cases_within_three_times_the_float32_oracle(emul):
     RC.check_bar(emul, list(RC.LARGE), 'large')
 
