@@ -40,7 +40,7 @@ _INTS = {'int': (_I32, -2**31, 2**31 - 1), 'unsigned': (ctypes.c_uint, 0, 2**32 
          'long long': (_I64, -2**63, 2**63 - 1), 'unsigned long long': (ctypes.c_uint64, 0, 2**64 - 1)}
 _REALS = {'float': _F32, 'double': ctypes.c_double}
 # pointee -> the tensor dtypes a pointer to it admits (None: any).  A `T* const*` parameter is a HOST array and admits no tensor.
-_DTYPES = {'float': (torch.float32,), 'int': (torch.int32,), 'unsigned': (torch.int32,), 'int64_t': (torch.int64,), 'void': None,
+_DTYPES = {'float': (torch.float32,), 'double': (torch.float64,), 'int': (torch.int32,), 'unsigned': (torch.int32,), 'int64_t': (torch.int64,), 'void': None,
            'unsigned long long': (torch.int64,),      # packed 64-bit keys (z | id, edge hash): opaque to torch, whose callers allocate int64
            'unsigned char': (torch.uint8,),           # flag / mask bytes: callers convert bool masks to uint8 before the call
            'uint8_t': (torch.uint8,)}                 # marching-tets case codes and `used` marks, allocated uint8

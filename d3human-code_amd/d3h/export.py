@@ -85,3 +85,52 @@ def load_textured_mesh(obj_path, filter_mode='linear', clear_ks=False, device=No
     if m.v_nrm is None:
         m = _mesh.auto_normals(m)
     return _mesh.compute_tangents(m)
+
+
+def _per_level(texture_res, levels):
+    """one value -- an int or an (H, W) pair of ints -- for every level, or a sequence of `levels` such values (a pair of ints is always (H, W))"""
+    one = lambda r: isinstance(r, int) or (isinstance(r, (list, tuple)) and len(r) == 2 and all(isinstance(x, int) for x in r))
+    if one(texture_res):
+        return [texture_res] * levels
+    if not isinstance(texture_res, (list, tuple)) or len(texture_res) != levels or not all(one(r) for r in texture_res):
+        raise ValueError(f'lod_chain: texture_res must be one resolution or one per level ({levels}), got {texture_res!r}')
+    return list(texture_res)
+
+
+@torch.no_grad()
+def lod_chain(mesh, material, face_counts, texture_res, kd_min, kd_max, ks_min, ks_max, nrm_min, nrm_max, **decimate_kw):
+    """A chain of levels of detail of a fitted mesh, each a textured_mesh of its own: fewer faces give the triangle-pair atlas larger cells, so a
+    coarser level uses its maps better ((s - 4)^2 / s^2 of a cell carries surface: 25 % at 131 072 faces on 2048^2, 67 % at 16 384).
+    face_counts: absolute, strictly decreasing, one per level.  Level 0 is textured_mesh(mesh, ...) whatever face_counts[0] says; level i is
+    d3h.meshrefine.decimate (quadric error metric, **decimate_kw passed on) of level i - 1's geometry down to face_counts[i], then auto_normals, then
+    textured_mesh with the same material: the material is volumetric (an MLPTexture3D under 'kd_ks'), so a coarse level gets its colours by
+    sampling it at its OWN surface -- nothing is baked from fine to coarse, and every level keeps the flat (0, 0, 1) normal map.  A count that
+    decimation cannot reach is no error: the level's real count is on its mesh.  texture_res: one resolution (an int or (H, W)) or one per level.
+    -> [Mesh, ...].  A material without 'kd_ks' (2-D maps) raises."""
+    from . import meshrefine as _MR
+    counts = [int(c) for c in face_counts]
+    if not counts or counts[-1] < 0 or any(b >= a for a, b in zip(counts, counts[1:])):
+        raise ValueError(f'lod_chain: face_counts must be non-negative and strictly decreasing, got {list(face_counts)!r}')
+    if 'kd_ks' not in material:
+        raise ValueError("lod_chain: the material must be volumetric ('kd_ks'); 2-D maps cannot be sampled at a coarser surface")
+    res = _per_level(texture_res, len(counts))
+    ranges = (kd_min, kd_max, ks_min, ks_max, nrm_min, nrm_max)
+    chain = [textured_mesh(mesh, material, res[0], *ranges)]
+    v = (mesh.v_pos[0] if mesh.v_pos.dim() == 3 else mesh.v_pos).detach().float().contiguous()
+    f = mesh.t_pos_idx
+    for count, r in zip(counts[1:], res[1:]):
+        v, f, _, _, _ = _MR.decimate(v, f, count, **decimate_kw)
+        chain.append(textured_mesh(_mesh.auto_normals(_mesh.Mesh(v, f, material=material)), material, r, *ranges))
+    return chain
+
+
+def write_lod_chain(folder, chain):
+    """folder/lod{i}/mesh.obj + mesh.mtl + the three maps of every level, through render.obj.write_obj; load_textured_mesh reads each back.
+    -> the folders written"""
+    out = []
+    for i, level in enumerate(chain):
+        sub = os.path.join(folder, f'lod{i}')
+        os.makedirs(sub, exist_ok=True)
+        _obj.write_obj(sub, level)
+        out.append(sub)
+    return out

@@ -77,7 +77,67 @@ The other steps of isotropic remeshing (csrc/meshremesh.hip), all opt-in.  Share
         collapse survivor whose position changed, a smoothed vertex) goes to (b0 A + b1 B) + b2 C, raytrace.Bvh.nearest's closest point on the
         INPUT surface (one Bvh of the input per call, or the caller's accel_bvh of that same input; tri == -1 leaves the vertex).  A pin_mask follows the
         vertices through the splits (new midpoints are not pinned) and through vmap.  (The 4/3 and 4/5 products are formed in double precision
-        and rounded to float32 once.)"""
+        and rounded to float32 once.)
+
+Quadric decimation (csrc/meshdecim.hip) for the level-of-detail export (d3h.export.lod_chain): the shape-keeping way to fewer faces, where
+collapse_short_edges is the uniform-length step of remeshing.  Conventions as above (adjacency, selection, validation) except where stated.
+
+    decimate(v, faces, target_faces, rounds=256, window=3.0, min_window=256, boundary='slide', max_cost=inf, pin_mask=None)
+            -> (v', f', parent, vmap, info)
+        v', f', parent, vmap as for collapse_short_edges.  info = {'rounds': rounds that collapsed something, 'collapses': their collapses,
+        'reached': F' <= target_faces + 1 (a collapse of an interior edge takes two faces, so an odd distance stops one short), 'max_cost': the
+        largest float64 cost taken (0.0 when nothing collapsed)}.  F <= target_faces returns the input.  F' >= target_faces always.
+        arithmetic    quadrics, placement and cost in float64 (positions promoted from float32), every operation rounded once in the order
+                      written, no contraction, dot / cross / len2 as above and
+                        det3(m) = (m00 (m11 m22 - m12 m21) - m01 (m10 m22 - m12 m20)) + m02 (m10 m21 - m11 m20)
+                        E(Q, q): r = ((a00 x + a01 y) + a02 z, (a01 x + a11 y) + a12 z, (a02 x + a12 y) + a22 z);
+                                 e = (((x rx + y ry) + z rz) + 2 ((b0 x + b1 y) + b2 z)) + c;  e < 0 gives 0
+                      for a quadric Q = (a00, a01, a02, b0, a11, a12, b1, a22, b2, c) and q = (x, y, z), a float32 point promoted.  The normal
+                      test is the float32 cosine test above at c2 = 0.04f (cos >= 0.2).
+        quadrics      built ONCE, from the input mesh, one thread per vertex as a gather (no float atomics): Q[i] = the sum from 0, over the faces
+                      of i in ascending index, of w (ux ux, ux uy, ux uz, ux d, uy uy, uy uz, uy d, uz uz, uz d, d d) -- each product formed, then
+                      times w -- with n = cross(p1 - p0, p2 - p0) of the face's rows, l = sqrt(dot(n, n)), u = n / l, d = -dot(u, p0), w = l * 0.5
+                      (l == 0, or not l > 0: the face adds nothing).  With boundary='slide' every edge (a, b) = (min, max) of face count 1 then
+                      adds, to both ends, in ascending edge rank, the plane through the edge perpendicular to its face (the first face of the
+                      vertex, in ascending index, that holds the other end; none if that face has l == 0): e = p[b] - p[a], m = cross(e, u),
+                      lm = sqrt(dot(m, m)) (0: nothing), m / lm in the place of u, d = -dot(m / lm, p[a]), w = 4 dot(e, e) (the 4 is
+                      DC_BOUNDARY_WEIGHT of the source).  Quadrics travel with the vertices: a collapse leaves Q[a] + Q[b] (a = min first) on its
+                      survivor; nothing is recomputed from the reduced mesh.
+        classes       per round, from the faces as they stand.  Pinned: on an edge of face count > 2, on an edge with min == max, on a number of
+                      edges of face count 1 other than 0 or 2, or set in pin_mask (which follows the vertices); with boundary='pin' every
+                      vertex on an edge of face count 1.  Boundary: on exactly two edges of face count 1, not pinned.  Interior: the rest.  Pinned
+                      vertices come back bit-unchanged and never disappear; boundary vertices thin out and never move.
+        candidates    edge (a, b) = (min, max), a != b, Qe = Q[a] + Q[b], of one of three kinds:
+                        face count 2, both ends interior: A = Qe's 3 x 3 part, det = det3(A), t = (a00 + a11) + a22, x = the solution of
+                          A x = -b by Cramer's rule (det3 with column k replaced, divided by det), mid = (v[a] + v[b]) * 0.5 in float64.  x is
+                          ACCEPTED when |det| > 1e-9 ((t t) t), x is finite and len2(x, mid) <= 4 len2(v[a], v[b]).  q = of x (if accepted), mid,
+                          v[a], v[b], each rounded to float32, the one of smallest E(Qe, q), a tie to the earlier in that list; survivor a
+                        face count 2, exactly one end interior: the other end survives where it is, q = its position (both ends boundary or
+                          pinned: a chord, no candidate)
+                        face count 1, boundary='slide', both ends boundary: q = v[b] if E(Qe, v[b]) < E(Qe, v[a]) else v[a]; that end survives
+                      with cost = E(Qe, q) finite and <= max_cost (a NaN or infinite cost is no candidate), and these checks on the round's
+                      input, before any claim (for the reason given under collapse_short_edges):
+                        link    N(a) and N(b) share exactly two vertices, each of valence > 3 (face count 2), or exactly one, of valence > 2
+                                (face count 1)
+                        normal  every face that holds a or b but not both passes the cosine test at c2 = 0.04f between nrm of its rows and nrm
+                                of its rows with that end replaced by q (a face of zero area fails it and so holds its corners in place)
+        window        need = ceil((F - target_faces) / 2), W = max(ceil(window * need), min_window).  Only the W candidates of smallest
+                      bits(float32(cost)) << 32 | rank place claims; the threshold is the W-th entry of a device sort, handed to the kernel as a
+                      device value (no read-back)
+        selection     key = (bits(float32(cost)) >> 20) << 32 | mix(rank, round) -- the cost's exponent and top three mantissa bits, ties
+                      broken by mix(rank, round): x = rank ^ (round * 0x9e3779b9); x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35;
+                      x ^= x >> 16 (32-bit, a bijection of the rank; round counts from 0) -- with the rank as tie-break a run of equal costs
+                      along the mesh yields one winner per round.  Claim set {a, b} + N(a) + N(b)
+        trim          the selected keys ascending; the longest prefix whose dropped faces (the edge's face count each) sum to at most
+                      F - target_faces collapses (a device scan, the cut handed to the kernel as a device value)
+        loop          ends when F' <= target_faces, when a round collapses nothing, or after `rounds` rounds; one read-back per round (collapses,
+                      dropped faces, error word, largest cost, together) and one for the quadrics' error word before the first.  Sizes
+                      (profiles/decimate_probe.md): a closed-neighbourhood claim lets a round take one to three percent of the edges, so 1/4
+                      of the faces takes about 50 to 140 rounds and 1/16 about 80 to 240, which is what rounds = 256 is for; min_window keeps
+                      the tail from starving when `need` gets small"""
+import math
+import struct
+
 import torch
 
 from . import _lib as L
@@ -359,3 +419,120 @@ def isotropic_remesh(v, faces, target_len, iterations=3, collapse_rounds=8, flip
         if reproject:
             v = _reproject(v, torch.nonzero(moved).reshape(-1), bvh, v0, f0)
     return v, f, parent
+
+
+# ---- quadric decimation (csrc/meshdecim.hip) ---------------------------------------------------------------------------------------------------
+
+class _DecimAdjacency(_Adjacency):
+    """_Adjacency plus what decimation reads (module docstring, "classes"): ncnt [nnbr] int32, the face count of the edge to each neighbour, and
+    vclass [n] uint8, 0 interior / 1 boundary / 2 pinned"""
+
+    def __init__(self, f, n, pin, slide):
+        super().__init__(f, n, None)
+        dev = f.device
+        elo, ehi, cnt = self.elo.long(), self.ehi.long(), self.ecnt.long()
+        own = torch.repeat_interleave(torch.arange(n, device=dev), (self.noffs[1:] - self.noffs[:-1]).long())
+        other = self.nbr.long()
+        rank = torch.searchsorted((elo << 32) | ehi, (torch.minimum(own, other) << 32) | torch.maximum(own, other))
+        self.ncnt = self.ecnt[rank].contiguous()
+        pinned = torch.zeros(n, dtype=torch.bool, device=dev) if pin is None else pin.clone()
+        fixed = (cnt > 2) | (elo == ehi)
+        pinned[elo[fixed]] = True
+        pinned[ehi[fixed]] = True
+        open_ = (cnt == 1) & (elo != ehi)
+        nopen = torch.bincount(torch.cat([elo[open_], ehi[open_]]), minlength=n)
+        pinned |= (nopen != 0) & (nopen != 2) if slide else nopen != 0
+        self.vclass = torch.where(pinned, 2, torch.where(nopen == 2, 1, 0)).to(torch.uint8).contiguous()
+
+
+def _decimate_round(v, f, Q, pin, target, window, min_window, slide, max_cost, rnd):
+    """-> None when nothing collapsed, else (v', f', parent, vmap, keep, Q', collapses, largest cost)"""
+    dev = v.device
+    n, nf = int(v.shape[0]), int(f.shape[0])
+    idx64 = f.dtype == torch.int64
+    A = _DecimAdjacency(f, n, pin, slide)
+    ne = A.ne
+    wkey, ekey, skey = (torch.empty(ne, dtype=torch.int64, device=dev) for _ in range(3))
+    eq = torch.empty(ne, 3, dtype=torch.float32, device=dev)
+    esurv = torch.empty(ne, dtype=torch.int32, device=dev)
+    ecost = torch.empty(ne, dtype=torch.float64, device=dev)
+    claim = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.zeros(4, dtype=torch.int32, device=dev)
+    maxcost = torch.zeros(1, dtype=torch.int64, device=dev)
+    L.call('decim_cost', v, f, idx64, nf, n, A.elo, A.ehi, A.ecnt, ne, A.noffs, A.nbr, A.nnbr, A.foffs, A.vf, A.nvf, A.vclass, Q, max_cost, slide, rnd, wkey, ekey,
+           eq, esurv, ecost, counts)
+    need = (nf - target + 1) // 2
+    w = min(max(int(math.ceil(window * need)), min_window), ne)
+    wthr = torch.sort(wkey).values[w - 1:w].contiguous()                           # the window's threshold stays on the device
+    L.call('decim_claim', A.elo, A.ehi, ne, n, A.noffs, A.nbr, A.nnbr, wkey, wthr, ekey, claim)
+    L.call('decim_select', A.elo, A.ehi, ne, n, A.noffs, A.nbr, A.nnbr, ekey, claim, skey)
+    sk, order = torch.sort(skey)                                                   # the trim: selected keys ascending, the prefix that stays above the target
+    chosen = sk != _MAXKEY
+    fits = chosen & (torch.cumsum(torch.where(chosen, A.ecnt[order].long(), 0), 0) <= nf - target)
+    cut = torch.cat([sk, sk.new_full((1,), _MAXKEY)])[fits.sum().reshape(1)].contiguous()
+    vout, qout = v.clone(), Q.clone()
+    ident = torch.arange(n, dtype=torch.int32, device=dev)
+    remap = ident.clone()
+    fdrop = torch.zeros(nf, dtype=torch.uint8, device=dev)
+    L.call('decim_apply', f, idx64, nf, n, A.elo, A.ehi, ne, A.foffs, A.vf, A.nvf, Q, skey, cut, eq, esurv, ecost, vout, qout, remap, fdrop, counts, maxcost)
+    nc, nd, word, _, bits = torch.cat([counts.long(), maxcost]).tolist()           # the round's one read-back
+    _mt._raise(word, 'decimate')
+    if nc == 0:
+        return None
+    keep = remap == ident
+    newidx = (torch.cumsum(keep, 0) - 1).int().contiguous()
+    kf = (fdrop == 0).long()
+    offs = (torch.cumsum(kf, 0) - kf).contiguous()
+    nout = nf - nd
+    fout = torch.empty(nout, 3, dtype=f.dtype, device=dev)
+    parent = torch.empty(nout, dtype=torch.int32, device=dev)
+    L.call('remesh_collapse_faces', f, idx64, nf, n, remap, newidx, fdrop, offs, nout, fout, parent)
+    return (vout[keep].contiguous(), fout, parent.long(), newidx[remap.long()].long(), keep, qout[keep].contiguous(), nc,
+            struct.unpack('<d', struct.pack('<q', bits))[0])
+
+
+def _quadrics(v, f, slide):
+    """Q [n,10] float64 of the mesh (module docstring, "quadrics")"""
+    n, nf = int(v.shape[0]), int(f.shape[0])
+    A = _DecimAdjacency(f, n, None, slide)
+    Q = torch.empty(n, 10, dtype=torch.float64, device=v.device)
+    counts = torch.zeros(4, dtype=torch.int32, device=v.device)
+    L.call('decim_quadrics', v, f, f.dtype == torch.int64, nf, n, A.noffs, A.nbr, A.ncnt, A.nnbr, A.foffs, A.vf, A.nvf, slide, Q, counts)
+    return Q, counts
+
+
+def decimate(v, faces, target_faces, rounds=256, window=3.0, min_window=256, boundary='slide', max_cost=float('inf'), pin_mask=None):
+    v, f, pin = _check('decimate', v, faces, pin_mask)
+    target, rounds, window, min_window, max_cost = int(target_faces), int(rounds), float(window), int(min_window), float(max_cost)
+    if target < 0:
+        raise RuntimeError(f'decimate: target_faces must be >= 0, got {target_faces}')
+    if not window > 0.0 or min_window < 1:
+        raise RuntimeError(f'decimate: window must be > 0 and min_window >= 1, got {window}, {min_window}')
+    if boundary not in ('slide', 'pin'):
+        raise RuntimeError(f"decimate: boundary must be 'slide' or 'pin', got {boundary!r}")
+    if not max_cost >= 0.0 or rounds < 0:
+        raise RuntimeError(f'decimate: max_cost and rounds must be >= 0, got {max_cost}, {rounds}')
+    dev = v.device
+    slide = boundary == 'slide'
+    parent = torch.arange(f.shape[0], dtype=torch.int64, device=dev)
+    vmap = torch.arange(v.shape[0], dtype=torch.int64, device=dev)
+    info = {'rounds': 0, 'collapses': 0, 'reached': True, 'max_cost': 0.0}
+    if f.shape[0] <= target:
+        return v, f, parent, vmap, info
+    Q, counts = _quadrics(v, f, slide)
+    _mt._raise(int(counts[2]), 'decimate')                                         # once per call, before the rounds
+    for rnd in range(rounds):
+        if f.shape[0] <= target:
+            break
+        r = _decimate_round(v, f, Q, pin, target, window, min_window, slide, max_cost, rnd)
+        if r is None:
+            break
+        v, f, p, m, keep, Q, nc, cost = r
+        parent, vmap = parent[p], m[vmap]
+        if pin is not None:
+            pin = pin[keep]
+        info['rounds'] += 1
+        info['collapses'] += nc
+        info['max_cost'] = max(info['max_cost'], cost)
+    info['reached'] = int(f.shape[0]) <= target + 1
+    return v, f, parent, vmap, info

@@ -28,6 +28,7 @@ GROUPS = {
     'meshtopo.hip': 'stage hand-off topology: script/connet_face_head.py:19-74 (UnionFind, find_connected_components), :97-112 (merge_and_repair_meshes: open3d remove_duplicated_vertices, un-vendored), script/process_body_cloth_head_msdfcut.py:92-102 (find_open_edges): lock-free union-find labelling, an exact-coordinate vertex weld and an edge-use count, each on an open-addressed table; error word bits 1 = face index out of range, 2 = iteration cap, 4 = table full',
     'meshrefine.hip': 'stage hand-off remeshing: the meshlabserver calls of script/process_body_cloth_head_msdfcut.py:621,625,661,715 with checkpoints/script/remesh.mlx (the refine step of isotropic remeshing) and :404-431 (process_subdivide) with midpoint_head.mlx (midpoint subdivision above an edge-length threshold): a conforming edge split on the edge table of meshtopo.hip, children in parent order; Jacobi relaxation of masked vertices for the caps of d3h/watertight.py (in place of the smoothness screened Poisson gives, wt.mlx)',
     'meshremesh.hip': 'stage hand-off remeshing, the rest of "Isotropic Explicit Remeshing" (checkpoints/script/remesh.mlx, the meshlabserver calls of script/process_body_cloth_head_msdfcut.py:621,625,661,715): edge collapse, edge flip and tangential smoothing on a sorted edge list and two CSR adjacencies, independent operations selected by a 64-bit atomic minimum per vertex (bit-reproducible); the refine step is meshrefine.hip, the reprojection Bvh.nearest of bvhdist.hip; counts word 2 is the error word (bit 1 = an index out of range)',
+    'meshdecim.hip': 'level-of-detail export (no reference counterpart: train.py:198-246 writes the fitted mesh at one level of detail): quadric-error-metric edge collapse (Garland & Heckbert 1997) on the adjacency and the claim words of meshremesh.hip -- float64 quadrics gathered per vertex, cost and placement per edge, a cost window, selection by a 64-bit atomic minimum per vertex on (cost bucket, hashed rank), a trim to the target (bit-reproducible); face compaction is d3h_remesh_collapse_faces; counts word 2 is the error word (bit 1 = an index out of range)',
     'tetfill.hip': 'start-up: script/get_tet_smpl.py:9-27 (get_tet_mesh: tetgen behind pyvista, un-vendored) as called by geometry/hmsdf.py:239-249 -- not a constrained Delaunay mesh but a tet lattice clipped by the linear interpolant of a vertex field: inside vertices + the marching-tets cut vertices (same bits, same order), 0 / 1 / 3 / 3 / 1 children per parent, prisms split smallest id first; error word bit 1 = NaN in the field',
     'optim.hip': 'the optimiser step: train.py:747-748 (encoder gradient / 8), :759-768 (the two torch.optim.Adam steps of train.py:593-620), :788 + geometry/hmsdf.py:398-405 (clamp_deform)',
     'timing.hip': 'measurement only: per-launch HIP-event timing of selected kernels for bench.py (no reference counterpart; train.py:679,789-790 times whole iterations with time.time())',
@@ -37,7 +38,7 @@ GROUPS = {
     'texmat.hip': 'the 2-D material lookups of shade(), render/render.py:277 (interpolate of v_tex by t_tex_idx) + render/texture.py:59-67 (Texture2D.sample of kd, ks, normal) at level 0: texel coordinate and up to three bilinear lookups per pixel in one pass, map gradients by fp32 atomics',
     'texmlp.hip': 'render/mlptexture.py:91-107 (MLPTexture3D.sample): tiny-cuda-nn HashGrid encoding (:62-79, un-vendored) + _MLP (:18-41) + sigmoid range map',
 }
-ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'bvhdist.hip', 'envshade.hip', 'envlight.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'meshtopo.hip', 'meshrefine.hip', 'meshremesh.hip', 'tetfill.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'uvatlas.hip', 'texmat.hip', 'optim.hip', 'timing.hip']
+ORDER = ['sdf_mlp.hip', 'sdf_mlp_x3.hip', 'sdf_mlp_bwd.hip', 'marching_tets.hip', 'lbs.hip', 'smplx_pose.hip', 'raster.hip', 'texture.hip', 'aux_buffers.hip', 'material_grads.hip', 'image_ops.hip', 'bsdf.hip', 'cubemap.hip', 'bvh.hip', 'bvhdist.hip', 'envshade.hip', 'envlight.hip', 'denoise.hip', 'lpips_head.hip', 'act_ops.hip', 'mesh_ops.hip', 'meshtopo.hip', 'meshrefine.hip', 'meshremesh.hip', 'meshdecim.hip', 'tetfill.hip', 'texmlp.hip', 'gridenc.hip', 'fusedmlp.hip', 'uvatlas.hip', 'texmat.hip', 'optim.hip', 'timing.hip']
 head = '''/* d3h.h -- C ABI of libd3h_hip.so: the MI355X (gfx950) hot path of D3-Human's render-and-fit loop.
  * GENERATED by tools/gen_header.py from the extern "C" definitions in d3human-code_amd/csrc/ -- do not edit by hand.
  *
